@@ -2,7 +2,21 @@
 """Benchmark of the MI355X-native reduction collective (BASELINE.json metric:
 "GiB/s device-resident float32 sum-reduce at 1/2/4/8 PEs vs HBM+xGMI roofline").
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--mib 1024]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--mib 1024] [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs: set-up, W warm-up steps, the K timed steps, the
+dump of the timed dest if --dump-outputs is given, and the one JSON line (value, ms_per_step, the
+roofline of the timed kernel from its HIP-event duration).  --full adds every other leg described
+below: the every-word check of the timed dest, the combine unit, the CPU baselines, the
+host-memory end-to-end legs and, at N>1, the phase breakdown, the xGMI probe, the launch-shape
+sweep, the coherence tripwire, the config-5 sweep and the RCCL comparison (each with its --no-*
+switch, as before).
+
+--dump-outputs DIR writes what the last timed step left in dest, as the caller of the reduce
+receives it: DIR/dest_pe<rank>.npy (float32).  A payload above the dump's budget (48 MiB over all
+ranks) is sampled in fixed 64 Ki-element windows: the first, the last, and seeded offsets between
+(dump_windows), the same in every run of the same arguments; the inputs are a closed-form pattern
+(ishmem_amd/selfcheck.py), so two builds can be compared output for output.
 
 N=1 (BASELINE configs[1]): ishmem_float_sum_reduce over a 1 GiB symmetric-heap array on one PE
 (reference semantics: dest = source, src/collectives/reduce_impl.h:288-289), plus the local
@@ -17,9 +31,9 @@ between barrier + device synchronize on both sides; ms_per_step is the max over 
   value       = N * B / t  (whole job: payload bytes of all PEs per second)
   algbw_GiBps = B / t      (per PE, the reference harness's payload rate,
                             test/include/ishmem_tester.h:1553-1555; SURVEY.md §8(d)'s targets)
-The dominant kernel's duration is measured with HIP events on the stream it runs on.  The timed
-dest is compared in full on every rank with the team-order fold of the rotating-winner
-input pattern (ishmem_amd/selfcheck.py).  Rank 0 (every rank at N>1) also
+The dominant kernel's duration is measured with HIP events on the stream it runs on.  With --full
+the timed dest is compared in full on every rank with the team-order fold of the rotating-winner
+input pattern (ishmem_amd/selfcheck.py), and rank 0 (every rank at N>1) also
 times the reference's host path — 64 KiB chunks, each through a synchronous device->host copy, the
 MPI-style shared-memory allreduce over the p PEs and a synchronous host->device copy
 (reduce_impl.h:186-228, memory.cpp:310-321) — restated in oracle/ (cpu_baseline).
@@ -788,12 +802,46 @@ def e2e_leg(ish, hip, n, B, world, rank, dist, stream, barrier, steps, pinned: b
         return {"error": str(ex)}
 
 
+DUMP_MAX_BYTES = 48 << 20   # --dump-outputs: all ranks' files together (the limit is 64 MB)
+DUMP_WINDOW = 1 << 16       # elements per sampled window
+
+
+def dump_windows(n: int, world: int) -> list[tuple[int, int]]:
+    """(first element, count) of the pieces of an n-element f32 dest that --dump-outputs keeps on
+    each rank: all of it within the rank's share of DUMP_MAX_BYTES, else DUMP_WINDOW-element
+    windows — the first, the last and seeded (fixed) starts between, in ascending order."""
+    share = DUMP_MAX_BYTES // 4 // world
+    if n <= share:
+        return [(0, n)]
+    k = max(2, share // DUMP_WINDOW)
+    starts = {0, n - DUMP_WINDOW}
+    starts.update(int(x) for x in np.random.default_rng(20240).integers(0, n - DUMP_WINDOW, k - 2))
+    return [(s, DUMP_WINDOW) for s in sorted(starts)]
+
+
+def dump_outputs(hip, dst: int, n: int, rank: int, world: int, outdir: str) -> dict:
+    """Write this rank's dest (what the last timed step computed) to outdir/dest_pe<rank>.npy."""
+    wins = dump_windows(n, world)
+    arr = np.concatenate([hip.download(dst + 4 * lo, m, np.float32) for lo, m in wins])
+    Path(outdir).mkdir(parents=True, exist_ok=True)
+    np.save(Path(outdir) / f"dest_pe{rank}.npy", arr)
+    return {"file": f"dest_pe{rank}.npy", "dtype": "float32", "elements": int(arr.size),
+            "sampled": len(wins) > 1, "windows": len(wins)}
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--mib", type=int, default=1024, help="payload per PE in MiB (default 1 GiB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline figure: the every-word check of the timed "
+                         "dest, combine, CPU baselines, host-memory end-to-end and, at N>1, phases, xGMI "
+                         "probe, launch-shape sweep, tripwire, config-5 sweep and RCCL (see the --no-* switches)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the dest of the last timed step to DIR/dest_pe<rank>.npy (float32; a fixed "
+                         "seeded sample of windows when the payload exceeds the dump's budget)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-combine", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
@@ -807,6 +855,8 @@ def main() -> int:
                     help="N>1: skip the RCCL all_reduce comparison on the same payload")
     ap.add_argument("--no-tuning", action="store_true", help="N>1: skip the launch-shape sweep")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(args)
@@ -914,21 +964,32 @@ def main() -> int:
     if ish.lib().ishmemi_c_error_count():
         raise RuntimeError("device barrier timeouts during the benchmark")
 
-    # Correctness of the timed buffers: every word of dest on every rank.
-    log("full check of the timed dest")
-    if args.no_full_check:
+    dumped = None
+    if args.dump_outputs:  # before any other leg writes dest
+        log("dump of the timed dest")
+        dumped = dump_outputs(hip, dst, n, rank, world, args.dump_outputs)
+
+    # Correctness of the timed buffers (--full): every word of dest on every rank.
+    full = args.full
+    if not full:
+        bad = 0
+        checked = {"words": 0, "mode": "not compared (plain run; --full compares every word)"}
+    elif args.no_full_check:
+        log("sampled check of the timed dest")
         idx = np.random.default_rng(0).integers(0, n, 256)
         bad = sum(sc.count_wrong(hip, dst, "sum", np.float32, world, int(i), 1) for i in idx)
         checked = {"words": 256, "mode": "sampled"}
     else:
+        log("full check of the timed dest")
         bad = sc.count_wrong(hip, dst, "sum", np.float32, world, 0, n)
         checked = {"words": n, "mode": "every word, every rank",
                    "input": "rotating-winner pattern (non-periodic, distinct per PE)",
                    "checker": sc.checker_kind(np.float32)}
-    bad = int(max_over_ranks(dist, [float(bad)])[0])
-    if bad:
-        raise RuntimeError(f"benchmark result check failed: {bad} words wrong")
-    checked["wrong"] = 0
+    if full:
+        bad = int(max_over_ranks(dist, [float(bad)])[0])
+        if bad:
+            raise RuntimeError(f"benchmark result check failed: {bad} words wrong")
+        checked["wrong"] = 0
 
     ms_per_step = wall_s * 1000.0 / args.steps
     value = world * B / GiB / (ms_per_step / 1000.0)
@@ -956,7 +1017,7 @@ def main() -> int:
             extra["legs_skipped"] = "a PE recorded a device timeout; later GPU legs skipped"
         return not unhealthy
 
-    if world == 1 and not args.no_combine:
+    if full and world == 1 and not args.no_combine:
         log("combine leg")
         # Local combine unit dst = a + b at the same size (3B HBM bytes per launch).
         b2 = ish.ishmem_malloc(B)
@@ -976,14 +1037,14 @@ def main() -> int:
                             "frac": ach / HBM_PEAK_GBS, "traffic": pmc_traffic("combine2_1pe", B)}
         ish.ishmem_free(b2)
 
-    if world > 1 and healthy() and roof["kernel"].startswith("rs_phase"):
+    if full and world > 1 and healthy() and roof["kernel"].startswith("rs_phase"):
         log("phase breakdown")
         try:
             extra["phases"] = phase_breakdown(ish, B, world, share, dist, step, barrier)
         except Exception as ex:
             extra["phases"] = {"error": str(ex)}
 
-    if world > 1 and healthy() and not args.no_probe:
+    if full and world > 1 and healthy() and not args.no_probe:
         log("xGMI probe")
         try:
             probe = xgmi_probe(ish, hip, src, dst, B, world, rank, dist, stream, barrier)
@@ -996,7 +1057,7 @@ def main() -> int:
         except Exception as ex:
             extra["xgmi_probe"] = {"error": str(ex)}
 
-    if world > 1 and healthy() and not args.no_tuning:
+    if full and world > 1 and healthy() and not args.no_tuning:
         log("launch-shape sweep")
         try:
             extra["xgmi_tuning"] = xgmi_tuning(ish, hip, src, dst, B, world, dist, stream)
@@ -1005,7 +1066,7 @@ def main() -> int:
             extra["xgmi_tuning"] = {"error": str(ex)}
 
     cpu = None
-    if not args.no_cpu_baseline and (world > 1 or rank == 0):
+    if full and not args.no_cpu_baseline and (world > 1 or rank == 0):
         log("CPU baseline leg (reference host path with its 64 KiB device copies)")
         try:
             cpu, more = cpu_baseline_leg(ish, hip, src, dst, n, B, world, rank, dist, key)
@@ -1016,7 +1077,7 @@ def main() -> int:
     ish.ishmem_free(dst)
     ish.ishmem_free(src)
 
-    if world > 1 and healthy() and not args.no_tripwire:
+    if full and world > 1 and healthy() and not args.no_tripwire:
         log("coherence tripwire")
         from ishmem_amd import selfcheck
         try:
@@ -1046,7 +1107,7 @@ def main() -> int:
                 ish.set_param("phased_peer_nt", old_nt)
                 ish.set_param("phased_min_bytes", old_min)
 
-    if world > 1 and healthy() and not args.no_sweep:
+    if full and world > 1 and healthy() and not args.no_sweep:
         log("config-5 sweep")
         # BASELINE configs[4] (min/max/prod x int32/float64 across the PEs), 4 KiB .. 4 GiB per PE.
         try:
@@ -1054,7 +1115,7 @@ def main() -> int:
         except Exception as ex:
             extra["config5_sweep"] = {"error": str(ex)}
 
-    if not args.no_e2e and (world == 1 or healthy()):
+    if full and not args.no_e2e and (world == 1 or healthy()):
         # Last: its pipeline streams add hardware queues, which oversubscribe the scheduler when
         # several ranks share one GPU (same-device rehearsals) and slow every later leg there.
         log("host-memory end-to-end leg")
@@ -1085,14 +1146,15 @@ def main() -> int:
                                         "timed kernel moves 2 B per payload byte and does no f32 arithmetic; the "
                                         "f32 sum itself is timed in 'combine' (dst = a + b, 3 B per payload byte)"}
                           if world == 1 else {})},
-            "kernel_ms": kern_ms, "checked": checked, "targets": targets,
+            "kernel_ms": kern_ms, "full": full, "checked": checked, "targets": targets,
+            **({"outputs": {"dir": args.dump_outputs, **dumped}} if dumped else {}),
             **({"flag_memory": flag_memory} if world > 1 else {}),
             **({"topology": link_topology(hip, device, world)} if world > 1 and not same_device else {}),
             **({"dev_same_device": True} if same_device else {}),
             **({"dev_emulated_one_pe_per_gpu": True} if emulate_share1 else {}), "roofline": roof,
             "cpu_baseline": cpu, **extra,
         }
-    if world > 1 and not args.no_rccl and not same_device:
+    if full and world > 1 and not args.no_rccl and not same_device:
         log("RCCL comparison leg")
         rccl = rccl_allreduce(dist, device, n, B, world, args.steps, line)
         if line is not None:

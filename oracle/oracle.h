@@ -8,7 +8,7 @@
  *   1. oracle_pattern_{source,check} restate the reference's own known-answer generators
  *      (test/unit/reduce_{sum,prod,min,max,and,or,xor}.cpp create_*_pattern); the oracle's fold
  *      of the source patterns must equal the reference's check pattern (tests/test_oracle.py).
- *   2. tests/golden/golden_np<N>.npz hold MPI_Allreduce outputs of MPICH 3.3.2 (the arithmetic backend the
+ *   2. tests/golden/golden_np<N>_p<k>.npz hold MPI_Allreduce outputs of MPICH 3.3.2 (the arithmetic backend the
  *      reference's host path calls, src/runtime/runtime_mpi.cpp:802-812) produced by
  *      oracle/mpi_golden.c on the reference patterns and seeded inputs; the oracle must agree.
  * The reference itself (SYCL + Level Zero) cannot be compiled in this image.

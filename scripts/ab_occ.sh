@@ -9,7 +9,7 @@ VARIANTS="${*:-product=product occ3=build/ab/libishmem_amd_occ3.so}"
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export HSA_ENABLE_IPC_MODE_LEGACY=0 ISHMEM_BENCH_SAME_DEVICE=1
-LEGS="--no-cpu-baseline --no-sweep --no-probe --no-tuning --no-tripwire --no-e2e --no-rccl --no-full-check"
+LEGS="--full --no-cpu-baseline --no-sweep --no-probe --no-tuning --no-tripwire --no-e2e --no-rccl --no-full-check"
 for rep in 1 2; do
   for nv in $VARIANTS; do
     v=${nv%%=*}; lib=${nv#*=}

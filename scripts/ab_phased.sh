@@ -11,7 +11,7 @@ STEPS="${*:-tests bench sweep}"
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export HSA_ENABLE_IPC_MODE_LEGACY=0
-LEGS="--no-cpu-baseline --no-sweep --no-probe --no-tuning --no-tripwire --no-e2e --no-rccl --no-full-check"
+LEGS="--full --no-cpu-baseline --no-sweep --no-probe --no-tuning --no-tripwire --no-e2e --no-rccl --no-full-check"
 for s in $STEPS; do
   case $s in
   tests)

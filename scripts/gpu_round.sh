@@ -39,15 +39,15 @@ for s in $STEPS; do
                 -m gpu -x -v --timeout 800 --timeout-method thread -p no:cacheprovider -k randomised_protocol_stress -s ;;
     single) run pytest_single 900 python -m pytest tests/test_gpu_single.py -m gpu -x -q -p no:cacheprovider ;;
     multi)  run pytest_multi 1200 python -m pytest tests/test_gpu_multi.py -m gpu -x -q -p no:cacheprovider ;;
-    bench)  run bench 600 python bench.py --steps 20 --warmup 5 ;;
+    bench)  run bench 600 python bench.py --full --steps 20 --warmup 5 ;;
     local2|local4|local8)  # N-rank rehearsal on the one GPU (self-launched ranks, same device)
             np_=${s#local}
-            ISHMEM_BENCH_SAME_DEVICE=1 run bench_$s 900 python bench.py --gpus $np_ --steps 10 --warmup 3 \
+            ISHMEM_BENCH_SAME_DEVICE=1 run bench_$s 900 python bench.py --full --gpus $np_ --steps 10 --warmup 3 \
                 --mib ${MIB:-1024} --sweep-max-mib ${SWEEP_MIB:-4096} ;;
     elocal2|elocal4|elocal8)  # the same rehearsal with every rank on its own emulated GPU (test-hooks
             # library): the cross-device thresholds and `recommended` keys of one PE per GPU
             np_=${s#elocal}
-            ISHMEM_BENCH_SAME_DEVICE=1 ISHMEM_BENCH_EMULATE_SHARE1=1 run bench_$s 900 python bench.py --gpus $np_ \
+            ISHMEM_BENCH_SAME_DEVICE=1 ISHMEM_BENCH_EMULATE_SHARE1=1 run bench_$s 900 python bench.py --full --gpus $np_ \
                 --steps 10 --warmup 3 --mib ${MIB:-1024} --sweep-max-mib ${SWEEP_MIB:-256} --no-e2e --no-rccl ;;
     sweep1) run sweep1 300 python tools/sweep.py --max-mib 1024 ;;
     bw2)    # tests/cpp/reduce_bw.cpp at 2 PEs (all modes incl. device_multi_wg 1/2/4/8 groups), CSV
@@ -79,13 +79,13 @@ for s in $STEPS; do
             done ;;
     prof)   cd /tmp && export TMPDIR=/tmp
             run rocprof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o run --output-format csv -- \
-                python3 "$R/bench.py" --steps 10 --warmup 2 --no-cpu-baseline
+                python3 "$R/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline
             cd "$R" ;;
     pmc)    cd /tmp && export TMPDIR=/tmp
             run pmc_fetch 600 rocprofv3 --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o run --output-format csv -- \
-                python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline
+                python3 "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline
             run pmc_write 600 rocprofv3 --pmc WRITE_SIZE -d "$OUT/pmc_write" -o run --output-format csv -- \
-                python3 "$R/bench.py" --steps 3 --warmup 1 --no-cpu-baseline
+                python3 "$R/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline
             cd "$R" ;;
   esac
 done

@@ -8,7 +8,7 @@ OUT="$R/gpurun_out/$TAG"
 mkdir -p "$OUT"
 export HSA_ENABLE_IPC_MODE_LEGACY=0 ISHMEM_BENCH_SAME_DEVICE=1
 cd /tmp && export TMPDIR=/tmp
-ARGS="--gpus $NP --steps 10 --warmup 3 --mib $MIB --no-sweep --no-tuning --no-cpu-baseline --no-e2e --no-tripwire --no-probe --no-full-check"
+ARGS="--full --gpus $NP --steps 10 --warmup 3 --mib $MIB --no-sweep --no-tuning --no-cpu-baseline --no-e2e --no-tripwire --no-probe --no-full-check"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$OUT/trace" -o run --output-format csv -- \
     python3 "$R/bench.py" $ARGS > "$OUT/trace.log" 2>&1
 rc=$?; echo "trace rc=$rc"; tail -3 "$OUT/trace.log"

@@ -33,6 +33,21 @@ def _bench():
     return mod
 
 
+def test_dump_windows_are_fixed_and_within_the_budget():
+    # --dump-outputs: a dest within a rank's share of the budget is written whole; above it the
+    # same windows in every run (first, last, seeded starts between), all ranks within 64 MB.
+    b = _bench()
+    assert b.DUMP_MAX_BYTES <= 64 * 10**6
+    share = b.DUMP_MAX_BYTES // 4
+    assert b.dump_windows(1, 1) == [(0, 1)] and b.dump_windows(share, 1) == [(0, share)]
+    for n, world in ((share + 1, 1), (1 << 28, 1), ((1 << 28) + 3, 2), (1 << 28, 8), (1 << 30, 8)):
+        w = b.dump_windows(n, world)
+        assert w == b.dump_windows(n, world)
+        assert w[0] == (0, b.DUMP_WINDOW) and w[-1] == (n - b.DUMP_WINDOW, b.DUMP_WINDOW)
+        assert all(0 <= lo and lo + m <= n for lo, m in w) and w == sorted(set(w)) and len(w) > 2
+        assert world * sum(m for _, m in w) * 4 <= b.DUMP_MAX_BYTES
+
+
 def test_roofline_same_device_is_hbm_bound_and_at_most_one():
     # Round-2 rehearsal numbers: 2 PEs on one GPU, 1 GiB each, 1.0 ms per launch.  Against the
     # xGMI spec this read 6.17x "peak"; against the device's HBM it is a fraction below 1.

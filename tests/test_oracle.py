@@ -8,14 +8,12 @@
    bit-exact for integer types and FP min/max, within the order-independent bound for FP sum/prod.
 3. The host bounce path restatement (64 KiB chunks, reduce_impl.h:186-228) equals the fold.
 """
-from pathlib import Path
-
 import numpy as np
 import pytest
 
 import oracle
+from tests.golden_io import load_golden
 
-GOLDEN = Path(__file__).resolve().parent / "golden"
 VALID = [(op, dt) for op in range(7) for dt in range(10) if oracle.valid(op, dt)]
 
 
@@ -53,8 +51,8 @@ def test_device_fold_order_per_pe_fp_can_differ_but_ints_never():
 
 
 def _golden_cases(npes):
-    z = np.load(GOLDEN / f"golden_np{npes}.npz")
-    names = sorted({k.rsplit("__", 1)[0] for k in z.files})
+    z = load_golden(npes)
+    names = sorted({k.rsplit("__", 1)[0] for k in z})
     for nm in names:
         op, dt, n = (int(x) for x in z[nm + "__meta"])
         yield nm, op, dt, n, list(z[nm + "__in"]), z[nm + "__out"]
