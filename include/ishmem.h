@@ -352,6 +352,34 @@ inline int ishmem_broadcast(T *dest, const T *source, size_t nelems, int root)
     }
 ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_BCAST_TYPED, _, _)
 
+/* ---- alltoall (src/ishmem.h:707ff; pulled block by block here) --------------------
+ * nelems / nbytes per block; source symmetric-heap memory, dest disjoint from it. */
+inline int ishmem_alltoallmem(ishmem_team_t team, void *dest, const void *source, size_t nbytes)
+{
+    return ishmemi_c_alltoall(team, dest, source, nbytes);
+}
+inline int ishmem_alltoallmem(void *dest, const void *source, size_t nbytes)
+{
+    return ishmemi_c_alltoall(ISHMEM_TEAM_WORLD, dest, source, nbytes);
+}
+template <typename T>
+inline int ishmem_alltoall(ishmem_team_t team, T *dest, const T *source, size_t nelems)
+{
+    return ishmemi_c_alltoall(team, (void *) dest, (const void *) source, nelems * sizeof(T));
+}
+template <typename T>
+inline int ishmem_alltoall(T *dest, const T *source, size_t nelems)
+{
+    return ishmem_alltoall(ISHMEM_TEAM_WORLD, dest, source, nelems);
+}
+#define ISHMEMI_CXX_A2A_TYPED(TYPENAME, TYPE, UNUSED1, UNUSED2)                                     \
+    inline int ishmem_##TYPENAME##_alltoall(ishmem_team_t t, TYPE *d, const TYPE *s, size_t n)     \
+    {                                                                                              \
+        return ishmem_alltoall(t, d, s, n);                                                        \
+    }                                                                                              \
+    inline int ishmem_##TYPENAME##_alltoall(TYPE *d, const TYPE *s, size_t n) { return ishmem_alltoall(d, s, n); }
+ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_A2A_TYPED, _, _)
+
 /* Compiled as HIP: the device-callable half of this API (the reference's SYCL_EXTERNAL functions:
  * ishmem_my_pe / ishmem_<TN>_<op>_reduce / ... from inside a kernel, ishmemx_*_work_group). */
 #if defined(__HIP__)

@@ -208,6 +208,19 @@ int ishmemi_c_produce_u32(void *dst, const void *a, const void *b, size_t n, voi
 int ishmemi_c_fcollect(int team, void *dest, const void *source, size_t nbytes);
 int ishmemi_c_fcollect_on_stream(int team, void *dest, const void *source, size_t nbytes, int *ret,
                                  void *stream);
+/* alltoall: `nbytes` per block, p blocks in source and in dest; on member i (its index in the team)
+ * dest block j = block i of member j's source, j == i included (ishmem_<TN>_alltoall /
+ * ishmem_alltoallmem, src/ishmem.h:707ff, src/collectives/alltoall_impl.h,
+ * docs/source/collectives.rst:325-470; ishmemx_alltoallmem_on_queue, src/ishmemx.h).  On return
+ * dest is complete on this PE and source may be reused.  For teams of more than one PE: source is
+ * symmetric-heap memory (all p blocks; there is no staged path), dest device-writable, and
+ * [dest, dest + p*nbytes) does not overlap [source, source + p*nbytes).  The blocking call agrees on
+ * argument failures across the team before anything is launched (every member then fails); the
+ * stream-ordered call checks its own arguments and fails before any launch.  nbytes == 0 still
+ * synchronises the team.  *ret as for ishmemi_c_reduce_on_stream. */
+int ishmemi_c_alltoall(int team, void *dest, const void *source, size_t nbytes);
+int ishmemi_c_alltoall_on_stream(int team, void *dest, const void *source, size_t nbytes, int *ret,
+                                 void *stream);
 int ishmemi_c_collect(int team, void *dest, const void *source, size_t nbytes);
 /* collect enqueued on `stream` (ishmemx_<TN>_collect_on_queue, src/ishmemx.h): the members'
  * byte counts are exchanged on the device inside the launch, so the call returns at once.  *ret as

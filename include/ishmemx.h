@@ -285,6 +285,82 @@ inline int ishmemx_broadcast_on_stream(T *dest, const T *source, size_t nelems, 
         return ishmemx_broadcast_on_stream(dest, source, nelems, root, ret, stream);               \
     }
 ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_BCAST_ON_STREAM, _, _)
+
+/* alltoall on a stream (src/ishmemx.h ishmemx_alltoallmem_on_queue / <TN>_alltoall_on_queue), with
+ * and without a team, and with the reference's deps / returned event. */
+inline int ishmemx_alltoallmem_on_stream(ishmem_team_t team, void *dest, const void *source, size_t nbytes,
+                                         int *ret, hipStream_t stream)
+{
+    return ishmemi_c_alltoall_on_stream(team, dest, source, nbytes, ret, (void *) stream);
+}
+inline int ishmemx_alltoallmem_on_stream(void *dest, const void *source, size_t nbytes, int *ret, hipStream_t stream)
+{
+    return ishmemi_c_alltoall_on_stream(ISHMEM_TEAM_WORLD, dest, source, nbytes, ret, (void *) stream);
+}
+inline int ishmemx_alltoallmem_on_stream(ishmem_team_t team, void *dest, const void *source, size_t nbytes,
+                                         int *ret, hipStream_t stream, const hipEvent_t *deps, size_t ndeps,
+                                         hipEvent_t done)
+{
+    return ishmemi_cxx::with_events(stream, deps, ndeps, done, [&] {
+        return ishmemi_c_alltoall_on_stream(team, dest, source, nbytes, ret, (void *) stream);
+    });
+}
+inline int ishmemx_alltoallmem_on_stream(void *dest, const void *source, size_t nbytes, int *ret, hipStream_t stream,
+                                         const hipEvent_t *deps, size_t ndeps, hipEvent_t done)
+{
+    return ishmemx_alltoallmem_on_stream(ISHMEM_TEAM_WORLD, dest, source, nbytes, ret, stream, deps, ndeps, done);
+}
+template <typename T>
+inline int ishmemx_alltoall_on_stream(ishmem_team_t team, T *dest, const T *source, size_t nelems, int *ret,
+                                      hipStream_t stream)
+{
+    return ishmemi_c_alltoall_on_stream(team, (void *) dest, (const void *) source, nelems * sizeof(T), ret,
+                                        (void *) stream);
+}
+template <typename T>
+inline int ishmemx_alltoall_on_stream(T *dest, const T *source, size_t nelems, int *ret, hipStream_t stream)
+{
+    return ishmemx_alltoall_on_stream(ISHMEM_TEAM_WORLD, dest, source, nelems, ret, stream);
+}
+template <typename T>
+inline int ishmemx_alltoall_on_stream(ishmem_team_t team, T *dest, const T *source, size_t nelems, int *ret,
+                                      hipStream_t stream, const hipEvent_t *deps, size_t ndeps, hipEvent_t done)
+{
+    return ishmemi_cxx::with_events(stream, deps, ndeps, done, [&] {
+        return ishmemx_alltoall_on_stream(team, dest, source, nelems, ret, stream);
+    });
+}
+template <typename T>
+inline int ishmemx_alltoall_on_stream(T *dest, const T *source, size_t nelems, int *ret, hipStream_t stream,
+                                      const hipEvent_t *deps, size_t ndeps, hipEvent_t done)
+{
+    return ishmemx_alltoall_on_stream(ISHMEM_TEAM_WORLD, dest, source, nelems, ret, stream, deps, ndeps, done);
+}
+#define ISHMEMI_CXX_A2A_ON_STREAM(TYPENAME, TYPE, UNUSED1, UNUSED2)                                  \
+    inline int ishmemx_##TYPENAME##_alltoall_on_stream(ishmem_team_t team, TYPE *dest,              \
+                                                       const TYPE *source, size_t nelems, int *ret, \
+                                                       hipStream_t stream)                          \
+    {                                                                                              \
+        return ishmemx_alltoall_on_stream(team, dest, source, nelems, ret, stream);                \
+    }                                                                                              \
+    inline int ishmemx_##TYPENAME##_alltoall_on_stream(TYPE *dest, const TYPE *source,              \
+                                                       size_t nelems, int *ret, hipStream_t stream) \
+    {                                                                                              \
+        return ishmemx_alltoall_on_stream(dest, source, nelems, ret, stream);                      \
+    }                                                                                              \
+    inline int ishmemx_##TYPENAME##_alltoall_on_stream(ishmem_team_t team, TYPE *dest,              \
+        const TYPE *source, size_t nelems, int *ret, hipStream_t stream, const hipEvent_t *deps,    \
+        size_t ndeps, hipEvent_t done)                                                             \
+    {                                                                                              \
+        return ishmemx_alltoall_on_stream(team, dest, source, nelems, ret, stream, deps, ndeps, done); \
+    }                                                                                              \
+    inline int ishmemx_##TYPENAME##_alltoall_on_stream(TYPE *dest, const TYPE *source,              \
+        size_t nelems, int *ret, hipStream_t stream, const hipEvent_t *deps, size_t ndeps,          \
+        hipEvent_t done)                                                                           \
+    {                                                                                              \
+        return ishmemx_alltoall_on_stream(dest, source, nelems, ret, stream, deps, ndeps, done);   \
+    }
+ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_A2A_ON_STREAM, _, _)
 inline int ishmemx_team_sync_on_stream(ishmem_team_t team, int *ret, hipStream_t stream)
 {
     return ishmemi_c_team_sync_on_stream(team, ret, (void *) stream);

@@ -7,7 +7,7 @@
  *       of the group `grp` calls, on every PE of the team;
  *   ishmem_<TYPENAME>_<op>_reduce([team,] dest, source, nreduce) from ONE work-item (the
  *       reference's device-side blocking call, e.g. in a single_task: examples/6_team_split_strided.cpp:67);
- *   fcollect / collect / sum_inscan / sum_exscan / broadcast in the same forms;
+ *   fcollect / collect / alltoall / sum_inscan / sum_exscan / broadcast in the same forms;
  *   ishmem_my_pe / n_pes / team_my_pe / team_n_pes / team_translate_pe / ptr / info_get_*,
  *   ishmem_barrier_all / sync_all / team_sync and their *_work_group forms, ishmemx_print.
  * `grp` is a HIP cooperative group — cooperative_groups::thread_block (the reference's
@@ -31,7 +31,7 @@
  * `source` must have been written by the calling group or by earlier kernels (the start barrier
  * releases this group's own writes).  Returns 0, or nonzero if the library is not initialised or
  * a peer did not arrive within the library's timeout.  dest/source must be symmetric-heap
- * addresses; source and dest identical or disjoint (reduce), disjoint (scan, collect).
+ * addresses; source and dest identical or disjoint (reduce), disjoint (scan, collect, alltoall).
  */
 #ifndef ISHMEM_AMD_ISHMEMX_DEVICE_H
 #define ISHMEM_AMD_ISHMEMX_DEVICE_H
@@ -436,6 +436,38 @@ __device__ inline int collect_group(const ishmemi_c_device_ctx_t *c, int team, v
     return group_barrier<G>(c, team, 2, epoch, false) ? 0 : 1;
 }
 
+// alltoall (src/collectives/alltoall_impl.h): `nbytes` per block; this member pulls the block
+// meant for it (block `me`) out of every member's source into block j of its dest, peers in the
+// order me+1, me+2, ..., me (its own block last, a local copy).  Pull, like collect_group: no peer
+// stores into this PE's coarse-grained heap.  Same epoch and phase slots as collect_group.  dest
+// must not overlap source (a peer may still be reading it).
+template <typename G>
+__device__ inline int alltoall_group(const ishmemi_c_device_ctx_t *c, int team, void *dest, const void *source,
+                                     size_t nbytes)
+{
+    if (!c || team < 0 || team >= ISHMEMI_C_MAX_TEAMS) return 1;  // not initialised / bad handle
+    const int size = c->team_size[team], me = c->team_my_idx[team];
+    if (size <= 0 || me < 0) return 1;
+    const uint32_t epoch = group_epoch<G>(c, team);
+    if (size == 1) {
+        if (dest != source) group_copy<G>((const char *) source, (char *) dest, nbytes, false);
+        G::sync();
+        return 0;
+    }
+    // Start: every member's source is final (this group's own writes released).
+    if (!group_barrier<G>(c, team, 0, epoch, true)) return 1;
+    const int start = c->team_start[team], stride = c->team_stride[team];
+    const char *mine = (const char *) source + (size_t) me * nbytes;
+    if (nbytes)
+        for (int k = 1; k <= size; ++k) {
+            const int j = (me + k) % size;
+            const char *src = j == me ? mine : peer_addr(c, mine, start + j * stride);
+            group_copy<G>(src, (char *) dest + (size_t) j * nbytes, nbytes, j != me);
+        }
+    // End: no member returns while a peer may still read its source.
+    return group_barrier<G>(c, team, 2, epoch, false) ? 0 : 1;
+}
+
 // Prefix sum in team order: member me folds members 0..me (inclusive) or 0..me-1 (exclusive;
 // member 0 gets 0) element by element — the first term passes through unchanged, as in the host
 // scan.  dest must not overlap source (a peer may still be reading it).
@@ -719,6 +751,12 @@ __device__ inline int ishmemx_collect_work_group(int team, T *dest, const T *sou
                                                                   nelems * sizeof(T), false);
 }
 template <typename T, typename Group>
+__device__ inline int ishmemx_alltoall_work_group(int team, T *dest, const T *source, size_t nelems, const Group &)
+{
+    return ishmemx_dev::alltoall_group<ishmemx_dev::exec_t<Group>>(ishmemx_dev::ctx(), team, dest, source,
+                                                                   nelems * sizeof(T));
+}
+template <typename T, typename Group>
 __device__ inline int ishmemx_sum_inscan_work_group(int team, T *dest, const T *source, size_t nelems, const Group &)
 {
     return ishmemx_dev::scan_group<ishmemx_dev::exec_t<Group>, T>(ishmemx_dev::ctx(), team, dest, source, nelems,
@@ -757,6 +795,7 @@ __device__ inline int ishmemx_broadcast_work_group(int team, T *dest, const T *s
     }
 ISHMEMX_DEV_COLL_WORLD(fcollect)
 ISHMEMX_DEV_COLL_WORLD(collect)
+ISHMEMX_DEV_COLL_WORLD(alltoall)
 ISHMEMX_DEV_COLL_WORLD(sum_inscan)
 ISHMEMX_DEV_COLL_WORLD(sum_exscan)
 template <typename T, typename Group>
@@ -803,6 +842,7 @@ __device__ inline int ishmem_broadcast(T *dest, const T *source, size_t nelems, 
 #define ISHMEMX_DEV_COLL(TYPENAME, TYPE, UNUSED1, UNUSED2)                                          \
     ISHMEMX_DEV_COLL_TYPED_ONE(TYPENAME, TYPE, fcollect)                                            \
     ISHMEMX_DEV_COLL_TYPED_ONE(TYPENAME, TYPE, collect)                                             \
+    ISHMEMX_DEV_COLL_TYPED_ONE(TYPENAME, TYPE, alltoall)                                            \
     ISHMEMX_DEV_COLL_TYPED_ONE(TYPENAME, TYPE, sum_inscan)                                          \
     ISHMEMX_DEV_COLL_TYPED_ONE(TYPENAME, TYPE, sum_exscan)                                          \
     template <typename Group>                                                                      \
@@ -828,7 +868,26 @@ __device__ inline int ishmem_broadcast(T *dest, const T *source, size_t nelems, 
         return ishmem_broadcast<TYPE>(dest, source, nelems, root);                                 \
     }
 
-/* byte forms: fcollectmem / collectmem / broadcastmem */
+/* byte forms: fcollectmem / collectmem / alltoallmem / broadcastmem */
+template <typename Group>
+__device__ inline int ishmemx_alltoallmem_work_group(int team, void *dest, const void *source, size_t nbytes,
+                                                     const Group &)
+{
+    return ishmemx_dev::alltoall_group<ishmemx_dev::exec_t<Group>>(ishmemx_dev::ctx(), team, dest, source, nbytes);
+}
+template <typename Group>
+__device__ inline int ishmemx_alltoallmem_work_group(void *dest, const void *source, size_t nbytes, const Group &grp)
+{
+    return ishmemx_alltoallmem_work_group(ISHMEMI_C_TEAM_WORLD, dest, source, nbytes, grp);
+}
+__device__ inline int ishmem_alltoallmem(int team, void *dest, const void *source, size_t nbytes)
+{
+    return ishmemx_alltoallmem_work_group(team, dest, source, nbytes, ishmemx_dev::thread);
+}
+__device__ inline int ishmem_alltoallmem(void *dest, const void *source, size_t nbytes)
+{
+    return ishmemx_alltoallmem_work_group(ISHMEMI_C_TEAM_WORLD, dest, source, nbytes, ishmemx_dev::thread);
+}
 template <typename Group>
 __device__ inline int ishmemx_fcollectmem_work_group(int team, void *dest, const void *source, size_t nbytes,
                                                      const Group &)

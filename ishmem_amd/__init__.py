@@ -326,6 +326,26 @@ def fcollect_on_stream(dest: int, source: int, nbytes: int, ret: int | None, str
     return _L.ishmemi_c_fcollect_on_stream(team, dest, source, nbytes, ret or None, stream or None)
 
 
+def ishmem_alltoallmem(*args) -> int:
+    """ishmem_alltoallmem([team,] dest, source, nbytes) -> int (bytes per block; src/ishmem.h:707ff)."""
+    team, (dest, source, n) = (ISHMEM_TEAM_WORLD, args) if len(args) == 3 else (args[0], args[1:])
+    return _L.ishmemi_c_alltoall(team, dest, source, n)
+
+
+def alltoall_on_stream(dest: int, source: int, nbytes: int, ret: int | None, stream: int,
+                       team: int = ISHMEM_TEAM_WORLD, deps=(), done=None) -> int:
+    """ishmemx_alltoallmem_on_queue analogue: symmetric source, `nbytes` per block; `deps` / `done`
+    as for reduce_on_stream."""
+    st = stream or None
+    if deps:
+        hs = [_event_handle(e) for e in deps]
+        if _L.ishmemi_c_stream_wait_events(st, (ctypes.c_void_p * len(hs))(*hs), len(hs)):
+            return 1
+    if _L.ishmemi_c_alltoall_on_stream(team, dest, source, nbytes, ret or None, st):
+        return 1
+    return _L.ishmemi_c_stream_record_event(st, _event_handle(done)) if done is not None else 0
+
+
 def ishmem_broadcastmem(*args) -> int:
     """ishmem_broadcastmem([team,] dest, source, nbytes, root) -> int (src/ishmem.h:786, :813)."""
     team, (dest, source, n, root) = (ISHMEM_TEAM_WORLD, args) if len(args) == 4 else (args[0], args[1:])
@@ -358,6 +378,8 @@ def _make_coll(kind: str, dt: str, size: int):
             return _L.ishmemi_c_fcollect(team, dest, source, n * size)
         if kind == "collect":
             return _L.ishmemi_c_collect(team, dest, source, n * size)
+        if kind == "alltoall":
+            return _L.ishmemi_c_alltoall(team, dest, source, n * size)
         return _L.ishmemi_c_scan(team, DTYPES[dt], 1 if kind == "inscan" else 0, dest, source, n)
     return fn
 
@@ -369,7 +391,7 @@ _mod = sys.modules[__name__]
 for _tn in ARITH_TYPENAMES:  # the reference's fcollect / collect / scan lists = these 23 names
     for _kind, _name in (("fcollect", f"ishmem_{_tn}_fcollect"), ("collect", f"ishmem_{_tn}_collect"),
                          ("inscan", f"ishmem_{_tn}_sum_inscan"), ("exscan", f"ishmem_{_tn}_sum_exscan"),
-                         ("broadcast", f"ishmem_{_tn}_broadcast")):
+                         ("broadcast", f"ishmem_{_tn}_broadcast"), ("alltoall", f"ishmem_{_tn}_alltoall")):
         _f = _make_coll(_kind, TYPENAMES[_tn], _SIZES[TYPENAMES[_tn]])
         _f.__name__ = _name
         setattr(_mod, _name, _f)

@@ -56,6 +56,8 @@ PROTOTYPES = [
     ("ishmemi_c_produce_u32", _i, [_vp, _vp, _vp, _sz, _vp]),
     ("ishmemi_c_fcollect", _i, [_i, _vp, _vp, _sz]),
     ("ishmemi_c_fcollect_on_stream", _i, [_i, _vp, _vp, _sz, _vp, _vp]),
+    ("ishmemi_c_alltoall", _i, [_i, _vp, _vp, _sz]),
+    ("ishmemi_c_alltoall_on_stream", _i, [_i, _vp, _vp, _sz, _vp, _vp]),
     ("ishmemi_c_collect_on_stream", _i, [_i, _vp, _vp, _sz, _vp, _vp]),
     ("ishmemi_c_stream_wait_events", _i, [_vp, _vp, _sz]),
     ("ishmemi_c_stream_record_event", _i, [_vp, _vp]),

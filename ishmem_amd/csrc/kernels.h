@@ -132,11 +132,14 @@ struct LLArgs {
     //               result is 0);
     //   kLLCollect - member j's bytes land at dest + j * nbytes (fcollect);
     //   kLLBroadcast - member `root`'s bytes land at every member's dest; the others push one
-    //               token item (no source read) so every member still hears from every member.
+    //               token item (no source read) so every member still hears from every member;
+    //   kLLAlltoall - the item pushed to member j is read from block j of the source
+    //               (src + j * nbytes), member j's item lands at dest + j * nbytes; this member's
+    //               own block goes straight from src + me * nbytes to dest + me * nbytes.
     int mode;
     int root;
 };
-constexpr int kLLReduce = 0, kLLInscan = 1, kLLExscan = 2, kLLCollect = 3, kLLBroadcast = 4;
+constexpr int kLLReduce = 0, kLLInscan = 1, kLLExscan = 2, kLLCollect = 3, kLLBroadcast = 4, kLLAlltoall = 5;
 hipError_t launch_ll(int op, int dt, const LLArgs &a, hipStream_t s);
 
 // fcollect / collect (all-gather of the members' sources): member j's bytes land at

@@ -26,7 +26,8 @@
 //     nothing in either grid waits, so it runs at the streaming kernels' rate (round 3).
 //   * ll_kernel: small payloads (up to 512 KiB, 2 MiB / p) with no handshake at all: every member
 //     pushes its bytes as {4 B data, 32-bit epoch} granules into every peer's ring and folds what
-//     it receives; the same exchange carries small fcollect, sum scans and broadcasts (round 5).
+//     it receives; the same exchange carries small fcollect, sum scans and broadcasts (round 5),
+//     and small alltoalls, where each peer is pushed its own block of the source.
 //   * The barriers replace ishmemi_team_sync's psync counters (src/collectives/sync_impl.h:30-69)
 //     with epoch-tagged flags in fine-grained memory: one "started" flag per member, one
 //     "ready" flag per reduced segment (the RS -> AG hand-off) and one "done reading" flag per
@@ -1396,9 +1397,8 @@ __device__ __forceinline__ uint64_t fold8(uint64_t acc, uint64_t x)
 // sit at multiples of 8 bytes from element 0, so elements never straddle them whatever the
 // array's address; the address only picks the load width (round 5: 4-B aligned arrays — a float
 // array 4 B off an 8-B boundary — took the persistent kernel before, 8.5 vs 4.5 us at 64 KiB).
-__device__ __forceinline__ uint64_t ll_load(const LLArgs &a, uint64_t off, uint64_t valid)
+__device__ __forceinline__ uint64_t ll_load(const char *p, uint64_t valid)
 {
-    const char *p = a.src + off;
     if (valid == 8) {
         if (((uintptr_t) p & 7) == 0) return *(const uint64_t *) p;
         if (((uintptr_t) p & 3) == 0)
@@ -1436,14 +1436,20 @@ __global__ __launch_bounds__(kBlock) void ll_kernel(LLArgs a)
     const uint64_t sg = ll_sender_granules(p);  // granules per (parity, sender) slot
     const bool bcast = a.mode == kLLBroadcast;
     const bool has_src = !bcast || me == a.root;  // a broadcast's non-roots read no source
+    // Alltoall: member j is sent block j of the source (items count from each block's base, so a
+    // block base off the 8-B grid only narrows ll_load / ll_store); every other mode sends one item
+    // to all.
+    const bool a2a = a.mode == kLLAlltoall;
     bool ok = true;
     for (uint64_t item = first; item < nitems; item += stride) {
         if (!has_src && item != 0) break;  // non-root: the item-0 token only
         const uint64_t off = item * 8;
-        const uint64_t mine = has_src ? ll_load(a, off, a.nbytes - off < 8 ? a.nbytes - off : 8) : 0;
-        const uint64_t g0 = tag | (uint32_t) mine, g1 = tag | (uint32_t) (mine >> 32);
+        const uint64_t valid = a.nbytes - off < 8 ? a.nbytes - off : 8;
+        uint64_t mine = has_src && !a2a ? ll_load(a.src + off, valid) : 0;
         for (int j = 0; j < p; ++j) {
             if (j == me) continue;
+            if (a2a) mine = ll_load(a.src + (uint64_t) j * a.nbytes + off, valid);
+            const uint64_t g0 = tag | (uint32_t) mine, g1 = tag | (uint32_t) (mine >> 32);
             uint64_t *slot = a.peer_ring[j] + (par * (uint64_t) p + me) * sg;
             __hip_atomic_store(slot + ll_granule(item, 0), g0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             __hip_atomic_store(slot + ll_granule(item, 1), g1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1455,7 +1461,7 @@ __global__ __launch_bounds__(kBlock) void ll_kernel(LLArgs a)
     for (uint64_t item = first; item < nitems && ok; item += stride) {
         const uint64_t off = item * 8;
         const uint64_t valid = a.nbytes - off < 8 ? a.nbytes - off : 8;
-        const uint64_t mine = has_src ? ll_load(a, off, valid) : 0;
+        const uint64_t mine = has_src ? ll_load(a.src + (a2a ? (uint64_t) me * a.nbytes : 0) + off, valid) : 0;
         uint64_t acc = 0;  // an empty fold (member 0's exclusive scan) stores zeros
         for (int j = 0; j < p && ok; ++j) {
             // Broadcast: the root's items, plus every member's item-0 token.
@@ -1477,11 +1483,11 @@ __global__ __launch_bounds__(kBlock) void ll_kernel(LLArgs a)
                 }
                 x = (h0 & 0xffffffffull) | (h1 << 32);
             }
-            if (a.mode == kLLCollect) ll_store(a.dst + (uint64_t) j * a.nbytes + off, valid, x);
+            if (a.mode == kLLCollect || a2a) ll_store(a.dst + (uint64_t) j * a.nbytes + off, valid, x);
             else if (bcast) { if (j == a.root) ll_store(a.dst + off, valid, x); }
             else if (j <= last) acc = (j == 0) ? x : fold8<T, OP>(acc, x);
         }
-        if (ok && a.mode != kLLCollect && !bcast) ll_store(a.dst + off, valid, acc);
+        if (ok && a.mode != kLLCollect && !a2a && !bcast) ll_store(a.dst + off, valid, acc);
     }
     // *ret was zeroed by the caller: any thread that failed marks it (sticky over launches).
     if (!ok && a.ret) __hip_atomic_fetch_or(a.ret, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

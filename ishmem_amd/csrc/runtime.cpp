@@ -1484,6 +1484,83 @@ bool member_call(const State &s, int team)
     return s.initialized && team >= 0 && team < kMaxTeams && s.teams[team].valid && s.teams[team].my_idx >= 0;
 }
 
+// ---------------- alltoall (ishmem_alltoall, src/collectives/alltoall_impl.h) ----------------
+// Member i's dest block j = member j's source block i, `nbytes` per block, p blocks on each side.
+// Pull only: the reference's intra-node loop stores each block into the peer's dest
+// (alltoall_impl.h's per-PE put), which here would write a peer's coarse-grained heap; instead every
+// member reads the block meant for it out of each peer's source, like fcollect reads whole sources.
+// Link and HBM bytes per member equal fcollect's ((p-1)·B remote and B local read, p·B written), so
+// the three paths and their thresholds are fcollect's:
+//   granule  - B within ll_eligible and 2·B <= the ring capacity: ll_kernel in kLLAlltoall mode;
+//   handshake - one collect_kernel launch between launch_start / launch_finish, member j's source
+//              pointer set to its block `me`, dest offset j·B;
+//   phased   - p·B >= phased_min_bytes: team barrier, collect_phase(_realign)_kernel, team barrier.
+// Block addresses j·B fall on any 16-B phase, so the item width comes from the actual addresses
+// on both sides (collect_launch's unit; the realigned kernels when they differ).
+//
+// Local argument errors (p > 1, B > 0), as bits so the blocking call can exchange them.
+constexpr uint64_t kA2aSrcHeap = 1, kA2aDest = 2, kA2aOverlap = 4;
+uint64_t alltoall_arg_errors(const State &s, const Team &t, const void *dst, const void *src, size_t nbytes)
+{
+    const uint64_t total = (uint64_t) t.size * nbytes;
+    const char *d = (const char *) dst, *sp = (const char *) src;
+    uint64_t e = 0;
+    // Peers find their block at this source's offset in their own heap: all p blocks inside it.
+    if (!in_heap(s, sp) || total > (uint64_t) (s.heap + s.heap_size - sp)) e |= kA2aSrcHeap;
+    if (!dst || !device_writable(s, dst)) e |= kA2aDest;
+    if (d < sp + total && sp < d + total) e |= kA2aOverlap;
+    return e;
+}
+
+std::string alltoall_arg_message(uint64_t e)
+{
+    if (e & kA2aSrcHeap) return "alltoall: a member's source is not symmetric-heap memory (p blocks inside the heap; there is no staged path)";
+    if (e & kA2aDest) return "alltoall: a member's dest is not device-writable (heap, device or pinned host memory)";
+    return "alltoall: a member's dest overlaps its source";
+}
+
+// checked: the blocking call has already exchanged the members' argument errors.
+int alltoall_impl(int team, void *dst, const void *src, size_t nbytes, int *ret, hipStream_t st, bool blocking,
+                  bool checked)
+{
+    State &s = S();
+    std::lock_guard<std::mutex> lk(s.mu);
+    if (!s.initialized) return fail("alltoall: not initialized");
+    if (team < 0 || team >= kMaxTeams || !s.teams[team].valid || s.teams[team].my_idx < 0)
+        return fail("alltoall: invalid team or caller not a member");
+    Team &t = s.teams[team];
+    if (nbytes > 0 && (!dst || !src)) return fail("alltoall: null buffer");
+    if (t.size > 1 && nbytes > 0 && !checked) {
+        const uint64_t e = alltoall_arg_errors(s, t, dst, src, nbytes);
+        if (e) return fail(alltoall_arg_message(e));
+    }
+    if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));
+    if (t.size == 1) {
+        if (nbytes && dst != src && launch_copy(dst, src, nbytes, st)) return 1;
+    } else if (nbytes == 0) {
+        if (team_sync_locked(s, team, st, ret)) return 1;
+    } else if (ll_eligible(s, t, dst, src, nbytes) && 2 * nbytes <= ll_capacity(t.size)) {
+        if (reduce_ll(s, team, ISHMEMI_OP_OR, ISHMEMI_DT_UINT8, dst, src, nbytes, ret, st, kLLAlltoall)) return 1;
+    } else {
+        uint64_t nb[kMaxPes], off[kMaxPes];
+        const char *srcs[kMaxPes];
+        for (int j = 0; j < t.size; ++j) {
+            const char *pj = translate(s, src, t.start + j * t.stride);
+            if (!pj) return fail("alltoall: source not mapped for PE " + std::to_string(t.start + j * t.stride));
+            srcs[j] = pj + (uint64_t) t.my_idx * nbytes;
+            off[j] = (uint64_t) j * nbytes;
+            nb[j] = nbytes;
+        }
+        if (collect_launch(s, team, dst, nullptr, nb, ret, st, off, srcs)) return 1;
+    }
+    if (mark_stream(s, st)) return 1;
+    if (blocking) {
+        if (host_wait(s, st)) return 1;
+        if (check_team_errors(s, team)) return 1;
+    }
+    return 0;
+}
+
 int scan_impl(int team, int dt, int inclusive, void *dst, const void *src, size_t n, int *ret,
               hipStream_t st, bool blocking)
 {
@@ -3072,6 +3149,31 @@ int ishmemi_c_fcollect_on_stream(int team, void *dest, const void *source, size_
                                  void *stream)
 {
     return fcollect_impl(team, dest, source, nbytes, ret, (hipStream_t) stream, false);
+}
+
+int ishmemi_c_alltoall(int team, void *dest, const void *source, size_t nbytes)
+{
+    // The members agree on argument failures before anything is launched: one member's bad
+    // argument fails every member, and the team's epochs stay in step.
+    State &s = S();
+    bool checked = false;
+    if (member_call(s, team) && s.teams[team].size > 1 && nbytes > 0) {
+        const uint64_t e = alltoall_arg_errors(s, s.teams[team], dest, source, nbytes);
+        uint64_t all[kMaxPes], any = 0;
+        if (team_exchange(team, e ? (e | kAgreeFail) : 0, all)) return 1;
+        for (int j = 0; j < s.teams[team].size; ++j) any |= all[j];
+        if (any & kAgreeFail) return fail(alltoall_arg_message(any));
+        checked = true;
+    }
+    return alltoall_impl(team, dest, source, nbytes, nullptr, 0, true, checked);
+}
+
+int ishmemi_c_alltoall_on_stream(int team, void *dest, const void *source, size_t nbytes, int *ret,
+                                 void *stream)
+{
+    // Nothing can be exchanged on the host here: each member checks its own arguments and fails
+    // before any launch (as collect_on_stream does).
+    return alltoall_impl(team, dest, source, nbytes, ret, (hipStream_t) stream, false, false);
 }
 
 int ishmemi_c_collect(int team, void *dest, const void *source, size_t nbytes)
