@@ -380,6 +380,90 @@ inline int ishmem_alltoall(T *dest, const T *source, size_t nelems)
     inline int ishmem_##TYPENAME##_alltoall(TYPE *d, const TYPE *s, size_t n) { return ishmem_alltoall(d, s, n); }
 ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_A2A_TYPED, _, _)
 
+/* ---- put / get / p / g, _nbi, quiet / fence (src/ishmem.h:90-330, :1545-1550) -----------------
+ * Host forms; the device-callable forms of the same names are in ishmemx_device.h.  void, as in
+ * the reference: a failure leaves its reason in ishmemi_c_last_error().  dest of a put / source of
+ * a get: symmetric-heap address; the other side heap, device, pinned or (blocking forms) pageable
+ * host memory.  Completion and visibility: DESIGN.md §3b. */
+inline void ishmem_putmem(void *dest, const void *source, size_t nbytes, int pe)
+{
+    (void) ishmemi_c_put(dest, source, nbytes, pe);
+}
+inline void ishmem_getmem(void *dest, const void *source, size_t nbytes, int pe)
+{
+    (void) ishmemi_c_get(dest, source, nbytes, pe);
+}
+inline void ishmem_putmem_nbi(void *dest, const void *source, size_t nbytes, int pe)
+{
+    (void) ishmemi_c_put_nbi(dest, source, nbytes, pe);
+}
+inline void ishmem_getmem_nbi(void *dest, const void *source, size_t nbytes, int pe)
+{
+    (void) ishmemi_c_get_nbi(dest, source, nbytes, pe);
+}
+template <typename T>
+inline void ishmem_put(T *dest, const T *source, size_t nelems, int pe)
+{
+    (void) ishmemi_c_put((void *) dest, (const void *) source, nelems * sizeof(T), pe);
+}
+template <typename T>
+inline void ishmem_get(T *dest, const T *source, size_t nelems, int pe)
+{
+    (void) ishmemi_c_get((void *) dest, (const void *) source, nelems * sizeof(T), pe);
+}
+template <typename T>
+inline void ishmem_put_nbi(T *dest, const T *source, size_t nelems, int pe)
+{
+    (void) ishmemi_c_put_nbi((void *) dest, (const void *) source, nelems * sizeof(T), pe);
+}
+template <typename T>
+inline void ishmem_get_nbi(T *dest, const T *source, size_t nelems, int pe)
+{
+    (void) ishmemi_c_get_nbi((void *) dest, (const void *) source, nelems * sizeof(T), pe);
+}
+/* p / g: one element; the value travels through a host variable (pageable: the blocking path). */
+template <typename T>
+inline void ishmem_p(T *dest, T value, int pe)
+{
+    (void) ishmemi_c_put((void *) dest, (const void *) &value, sizeof(T), pe);
+}
+template <typename T>
+inline T ishmem_g(const T *source, int pe)
+{
+    T value = T();
+    (void) ishmemi_c_get((void *) &value, (const void *) source, sizeof(T), pe);
+    return value;
+}
+#define ISHMEMI_CXX_RMA_SIZED(BITS)                                                                 \
+    inline void ishmem_put##BITS(void *d, const void *s, size_t n, int pe) { ishmem_putmem(d, s, n * (BITS / 8), pe); } \
+    inline void ishmem_get##BITS(void *d, const void *s, size_t n, int pe) { ishmem_getmem(d, s, n * (BITS / 8), pe); } \
+    inline void ishmem_put##BITS##_nbi(void *d, const void *s, size_t n, int pe)                    \
+    {                                                                                              \
+        ishmem_putmem_nbi(d, s, n * (BITS / 8), pe);                                               \
+    }                                                                                              \
+    inline void ishmem_get##BITS##_nbi(void *d, const void *s, size_t n, int pe)                    \
+    {                                                                                              \
+        ishmem_getmem_nbi(d, s, n * (BITS / 8), pe);                                               \
+    }
+ISHMEMI_CXX_RMA_SIZED(8)
+ISHMEMI_CXX_RMA_SIZED(16)
+ISHMEMI_CXX_RMA_SIZED(32)
+ISHMEMI_CXX_RMA_SIZED(64)
+ISHMEMI_CXX_RMA_SIZED(128)
+/* The 23 RMA typenames of src/ishmem.h:91-113 are the arithmetic list above. */
+#define ISHMEMI_CXX_RMA_TYPED(TYPENAME, TYPE, UNUSED1, UNUSED2)                                     \
+    inline void ishmem_##TYPENAME##_put(TYPE *d, const TYPE *s, size_t n, int pe) { ishmem_put(d, s, n, pe); } \
+    inline void ishmem_##TYPENAME##_get(TYPE *d, const TYPE *s, size_t n, int pe) { ishmem_get(d, s, n, pe); } \
+    inline void ishmem_##TYPENAME##_put_nbi(TYPE *d, const TYPE *s, size_t n, int pe) { ishmem_put_nbi(d, s, n, pe); } \
+    inline void ishmem_##TYPENAME##_get_nbi(TYPE *d, const TYPE *s, size_t n, int pe) { ishmem_get_nbi(d, s, n, pe); } \
+    inline void ishmem_##TYPENAME##_p(TYPE *d, TYPE v, int pe) { ishmem_p(d, v, pe); }              \
+    inline TYPE ishmem_##TYPENAME##_g(const TYPE *s, int pe) { return ishmem_g(s, pe); }
+ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_RMA_TYPED, _, _)
+/* ishmem_quiet: every _nbi put / get issued so far by this PE is complete.  ishmem_fence: nothing to
+ * do on the host beyond validity (the _nbi stream is in order). */
+inline void ishmem_quiet(void) { (void) ishmemi_c_quiet(); }
+inline void ishmem_fence(void) { (void) ishmemi_c_fence(); }
+
 /* Compiled as HIP: the device-callable half of this API (the reference's SYCL_EXTERNAL functions:
  * ishmem_my_pe / ishmem_<TN>_<op>_reduce / ... from inside a kernel, ishmemx_*_work_group). */
 #if defined(__HIP__)

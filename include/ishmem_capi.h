@@ -245,6 +245,39 @@ int ishmemi_c_scan_on_stream(int team, int dtype, int inclusive, void *dest, con
 int ishmemi_c_stream_wait_events(void *stream, void *const *deps, size_t ndeps);
 int ishmemi_c_stream_record_event(void *stream, void *done);
 
+/* ---- put / get, quiet / fence — ishmem_put / ishmem_get / _nbi / ishmem_p / ishmem_g / ishmem_quiet /
+ *      ishmem_fence (src/ishmem.h:90-330, src/rma.cpp, src/nbi.cpp, src/memory_ordering.cpp) ------
+ * `nbytes` from `source` to `dest`; the REMOTE side (dest of a put, source of a get) is given as
+ * this PE's symmetric address and must lie inside the symmetric heap for its whole length; the local
+ * side is heap, device or pinned host memory (pageable host memory: blocking forms only, through
+ * hipMemcpy to / from the mapped peer address).  `pe` in [0, npes); pe == my_pe is a local copy.
+ * nbytes == 0 succeeds and launches nothing.  Item width comes from the addresses and the count.
+ *   put / get           return when the local buffer is reusable and the bytes are in the
+ *                       target's memory;
+ *   put_nbi / get_nbi   enqueue on a library-internal non-blocking stream, in call order, and
+ *                       return; ishmemi_c_quiet waits for that stream, ishmemi_c_barrier_all
+ *                       drains it too (barrier_all = quiet + sync_all; sync_all / team_sync do not);
+ *   put / get_on_stream enqueue on `stream` (hipStream_t), which orders them;
+ *   fence               nothing to do beyond validity: the internal stream is in order;
+ *   quiet_on_stream     `stream` waits for everything enqueued so far on the internal stream.
+ * Argument errors (pe out of range, remote side outside the heap, local side not device-accessible
+ * for _nbi / _on_stream, null pointer with nbytes > 0) return nonzero before anything is launched.
+ * Visibility on the target: DESIGN.md §3b. */
+int ishmemi_c_put(void *dest, const void *source, size_t nbytes, int pe);
+int ishmemi_c_get(void *dest, const void *source, size_t nbytes, int pe);
+int ishmemi_c_put_nbi(void *dest, const void *source, size_t nbytes, int pe);
+int ishmemi_c_get_nbi(void *dest, const void *source, size_t nbytes, int pe);
+int ishmemi_c_put_on_stream(void *dest, const void *source, size_t nbytes, int pe, void *stream);
+int ishmemi_c_get_on_stream(void *dest, const void *source, size_t nbytes, int pe, void *stream);
+int ishmemi_c_quiet(void);
+int ishmemi_c_fence(void);
+int ishmemi_c_quiet_on_stream(void *stream);
+/* Test hook (no reference counterpart): `grid` workgroups (<= 1024) that EACH read all n uint32 of p
+ * with ordinary loads and write their own copy, out[b * n + i] = p[i] (out: grid * n words) — a
+ * user's consumer kernel.  Before a peer's put it warms the caches of every CU it ran on with p's
+ * lines; after, it shows what plain loads see there.  Asynchronous on `stream`. */
+int ishmemi_c_read_all_u32(void *out, const void *p, size_t n, int grid, void *stream);
+
 /* ---- device-initiated collectives ----------------------------------------------------------
  * The reference's device-callable reductions (ishmemx_<TN>_<op>_reduce_work_group,
  * src/collectives/reduce_impl.h:386-418, :505-518, src/ishmemx.h:1648-1699) read the library

@@ -375,6 +375,72 @@ inline int ishmemx_barrier_all_on_stream(hipStream_t stream)
     return ishmemi_c_team_sync_on_stream(ISHMEM_TEAM_WORLD, nullptr, (void *) stream);
 }
 
+/* put / get on a stream (ishmemx_*_{put,get}[_nbi]_on_queue, src/ishmemx.h): enqueued on `stream`,
+ * which orders them, so the _nbi form coincides with the plain one; with the reference's deps /
+ * returned event as (deps, ndeps, done).  ishmemx_quiet_on_stream: `stream` waits for every host
+ * _nbi put / get issued so far. */
+#define ISHMEMI_CXX_RMA_ON_STREAM_MEM(NAME, CALL, MUL)                                              \
+    inline int ishmemx_##NAME##_on_stream(void *dest, const void *source, size_t n, int pe, hipStream_t stream) \
+    {                                                                                              \
+        return CALL(dest, source, n * (MUL), pe, (void *) stream);                                 \
+    }                                                                                              \
+    inline int ishmemx_##NAME##_on_stream(void *dest, const void *source, size_t n, int pe, hipStream_t stream, \
+                                          const hipEvent_t *deps, size_t ndeps, hipEvent_t done)   \
+    {                                                                                              \
+        return ishmemi_cxx::with_events(stream, deps, ndeps, done,                                 \
+                                        [&] { return CALL(dest, source, n * (MUL), pe, (void *) stream); }); \
+    }
+#define ISHMEMI_CXX_RMA_ON_STREAM_BOTH(SUFFIX, MUL)                                                 \
+    ISHMEMI_CXX_RMA_ON_STREAM_MEM(put##SUFFIX, ishmemi_c_put_on_stream, MUL)                        \
+    ISHMEMI_CXX_RMA_ON_STREAM_MEM(get##SUFFIX, ishmemi_c_get_on_stream, MUL)                        \
+    ISHMEMI_CXX_RMA_ON_STREAM_MEM(put##SUFFIX##_nbi, ishmemi_c_put_on_stream, MUL)                  \
+    ISHMEMI_CXX_RMA_ON_STREAM_MEM(get##SUFFIX##_nbi, ishmemi_c_get_on_stream, MUL)
+ISHMEMI_CXX_RMA_ON_STREAM_BOTH(mem, 1)
+ISHMEMI_CXX_RMA_ON_STREAM_BOTH(8, 1)
+ISHMEMI_CXX_RMA_ON_STREAM_BOTH(16, 2)
+ISHMEMI_CXX_RMA_ON_STREAM_BOTH(32, 4)
+ISHMEMI_CXX_RMA_ON_STREAM_BOTH(64, 8)
+ISHMEMI_CXX_RMA_ON_STREAM_BOTH(128, 16)
+#define ISHMEMI_CXX_RMA_ON_STREAM_T(NAME, CALL)                                                     \
+    template <typename T>                                                                          \
+    inline int ishmemx_##NAME##_on_stream(T *dest, const T *source, size_t nelems, int pe, hipStream_t stream) \
+    {                                                                                              \
+        return CALL((void *) dest, (const void *) source, nelems * sizeof(T), pe, (void *) stream); \
+    }                                                                                              \
+    template <typename T>                                                                          \
+    inline int ishmemx_##NAME##_on_stream(T *dest, const T *source, size_t nelems, int pe, hipStream_t stream, \
+                                          const hipEvent_t *deps, size_t ndeps, hipEvent_t done)   \
+    {                                                                                              \
+        return ishmemi_cxx::with_events(stream, deps, ndeps, done, [&] {                           \
+            return CALL((void *) dest, (const void *) source, nelems * sizeof(T), pe, (void *) stream); \
+        });                                                                                        \
+    }
+ISHMEMI_CXX_RMA_ON_STREAM_T(put, ishmemi_c_put_on_stream)
+ISHMEMI_CXX_RMA_ON_STREAM_T(get, ishmemi_c_get_on_stream)
+ISHMEMI_CXX_RMA_ON_STREAM_T(put_nbi, ishmemi_c_put_on_stream)
+ISHMEMI_CXX_RMA_ON_STREAM_T(get_nbi, ishmemi_c_get_on_stream)
+#define ISHMEMI_CXX_RMA_ON_STREAM_TYPED_ONE(TYPENAME, TYPE, NAME)                                   \
+    inline int ishmemx_##TYPENAME##_##NAME##_on_stream(TYPE *d, const TYPE *s, size_t n, int pe, hipStream_t st) \
+    {                                                                                              \
+        return ishmemx_##NAME##_on_stream<TYPE>(d, s, n, pe, st);                                  \
+    }                                                                                              \
+    inline int ishmemx_##TYPENAME##_##NAME##_on_stream(TYPE *d, const TYPE *s, size_t n, int pe, hipStream_t st, \
+                                                       const hipEvent_t *deps, size_t ndeps, hipEvent_t done) \
+    {                                                                                              \
+        return ishmemx_##NAME##_on_stream<TYPE>(d, s, n, pe, st, deps, ndeps, done);               \
+    }
+#define ISHMEMI_CXX_RMA_ON_STREAM_TYPED(TYPENAME, TYPE, UNUSED1, UNUSED2)                           \
+    ISHMEMI_CXX_RMA_ON_STREAM_TYPED_ONE(TYPENAME, TYPE, put)                                        \
+    ISHMEMI_CXX_RMA_ON_STREAM_TYPED_ONE(TYPENAME, TYPE, get)                                        \
+    ISHMEMI_CXX_RMA_ON_STREAM_TYPED_ONE(TYPENAME, TYPE, put_nbi)                                    \
+    ISHMEMI_CXX_RMA_ON_STREAM_TYPED_ONE(TYPENAME, TYPE, get_nbi)
+ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_RMA_ON_STREAM_TYPED, _, _)
+inline int ishmemx_quiet_on_stream(hipStream_t stream) { return ishmemi_c_quiet_on_stream((void *) stream); }
+inline int ishmemx_quiet_on_stream(hipStream_t stream, const hipEvent_t *deps, size_t ndeps, hipEvent_t done)
+{
+    return ishmemi_cxx::with_events(stream, deps, ndeps, done, [&] { return ishmemi_c_quiet_on_stream((void *) stream); });
+}
+
 /* Explicit-identity init (the role of ishmemx_init_attr, src/ishmemx.h:21-37). */
 inline int ishmemx_init_pe(int pe, int npes, int device, const char *bootstrap_key)
 {

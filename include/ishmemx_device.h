@@ -8,6 +8,8 @@
  *   ishmem_<TYPENAME>_<op>_reduce([team,] dest, source, nreduce) from ONE work-item (the
  *       reference's device-side blocking call, e.g. in a single_task: examples/6_team_split_strided.cpp:67);
  *   fcollect / collect / alltoall / sum_inscan / sum_exscan / broadcast in the same forms;
+ *   ishmem_<TYPENAME>_put / _get / _p / _g, their _nbi, sized and mem forms from any work-item,
+ *       ishmemx_*_{put,get}[_nbi]_work_group, ishmem_quiet / fence, ishmemx_quiet / fence_work_group;
  *   ishmem_my_pe / n_pes / team_my_pe / team_n_pes / team_translate_pe / ptr / info_get_*,
  *   ishmem_barrier_all / sync_all / team_sync and their *_work_group forms, ishmemx_print.
  * `grp` is a HIP cooperative group — cooperative_groups::thread_block (the reference's
@@ -241,7 +243,13 @@ __device__ inline bool group_barrier(const ishmemi_c_device_ctx_t *c, int team, 
                 __builtin_amdgcn_s_sleep(2);
             }
         }
+        // One system-scope acquire by the leader drops this CU's stale L1 lines (and the L2's
+        // non-coherent ones) for the whole group: bytes a peer PUT before the barrier are then read
+        // by plain loads.  The leader waits for the invalidate before the group's barrier inside
+        // bcast (a workgroup barrier waits for no memory counter), so every wave of the group, not
+        // only the leader's, loads behind it.
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     return G::bcast(ok) != 0;
 }
@@ -527,8 +535,9 @@ __device__ inline int scan_group(const ishmemi_c_device_ctx_t *c, int team, T *d
 
 // Team barrier from inside a kernel (ishmem_team_sync / sync_all / barrier_all and their
 // *_work_group forms, src/collectives/sync_impl.h:30-69): the group's writes are released, then
-// every member's group meets on the team's phase-3 row.  There is no RMA in this library, so
-// barrier_all's quiet has nothing further to complete.
+// every member's group meets on the team's phase-3 row.  The device put / get forms complete
+// eagerly (write-through stores, drained before they return), so barrier_all's quiet has nothing
+// further to complete beyond the wait and release at the head of group_barrier.
 template <typename G>
 __device__ inline int team_sync_group(const ishmemi_c_device_ctx_t *c, int team)
 {
@@ -565,6 +574,89 @@ __device__ inline int broadcast_group(const ishmemi_c_device_ctx_t *c, int team,
     if (root != me) group_copy<G>(peer_addr(c, source, groot), (char *) dest, nbytes, true);
     else if (dest != source) group_copy<G>((const char *) source, (char *) dest, nbytes, false);
     return group_barrier<G>(c, team, 2, epoch, false) ? 0 : 1;
+}
+
+// ---- put / get from inside a kernel (src/rma_impl.h:46-75, :116-145) -------------------------
+// `nbytes` between this PE's memory and a peer's mapped heap, spread over the group; the layout
+// follows the STORE side (head < 16 B up to dst's 16-B boundary, 16-B body, tail), the load side
+// is read at the same offsets (unaligned 16-B loads when it sits on another 16-B phase).
+//   PUT: plain local loads, remote stores system-coherent write-through (sc0 sc1);
+//   GET: remote loads system-coherent (sc0 sc1, never a warm L1 / L2 line), plain local stores.
+// A group's threads all pass the same pointers (scalar descriptor base); single work-items may
+// each pass their own, so thread_t keeps the base per lane.
+template <typename G>
+__device__ __forceinline__ const char *rma_base(const char *p)
+{
+    if constexpr (std::is_same_v<G, thread_t>) return p;
+    else return group_uniform(p);
+}
+
+template <typename G, bool PUT>
+__device__ inline void rma_group(char *dst, const char *src, size_t nbytes)
+{
+    const int tid = G::rank(), nthr = G::size();
+    size_t head = (16 - ((uintptr_t) dst & 15)) & 15;
+    if (head > nbytes) head = nbytes;
+    const size_t nv = (nbytes - head) / 16, tail = nbytes - head - nv * 16;
+    const char *sb = src + head;
+    char *db = dst + head;
+    for (size_t v0 = 0; v0 < nv; v0 += (size_t) nthr * kUnroll) {
+        const char *ls = rma_base<G>(sb + v0 * 16);
+        char *ds = (char *) rma_base<G>(db + v0 * 16);
+        const __amdgpu_buffer_rsrc_t lr =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<char *>(ls), (short) 0, 0x7FFFFFFF, 0x00020000);
+        Vec16<uint32_t> x[kUnroll];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const size_t k = (size_t) u * nthr + tid;
+            if (v0 + k < nv)
+                x[u] = __builtin_bit_cast(Vec16<uint32_t>,
+                                          __builtin_amdgcn_raw_buffer_load_b128(lr, (uint32_t) (k * 16), 0, PUT ? 0 : 17));
+        }
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const size_t k = (size_t) u * nthr + tid;
+            if (v0 + k >= nv) continue;
+            if constexpr (PUT) sys_store16<uint32_t>(ds, (uint32_t) (k * 16), x[u]);
+            else ((Vec16<uint32_t> *) ds)[k] = x[u];
+        }
+    }
+    for (size_t i = tid; i < head + tail; i += nthr) {
+        const size_t off = i < head ? i : nv * 16 + i;
+        if constexpr (PUT) sys_store((uint8_t *) dst + off, ((const uint8_t *) src)[off]);
+        else dst[off] = (char) sys_load((const uint8_t *) src + off);
+    }
+}
+
+// Blocking put / get by the group G (thread_t: one work-item): group sync, the copy, every
+// thread's accesses drained (a write-through store counts as done once memory has it), group sync.
+// The _nbi device forms are the same call: they complete eagerly.
+template <typename G, bool PUT>
+__device__ inline void rma_call(void *dest, const void *source, size_t nbytes, int pe)
+{
+    const ishmemi_c_device_ctx_t *c = ctx();
+    if (!c || pe < 0 || pe >= c->npes) return;
+    G::sync();
+    if (nbytes) {
+        if constexpr (PUT) rma_group<G, true>(peer_addr(c, dest, pe), (const char *) source, nbytes);
+        else rma_group<G, false>((char *) dest, peer_addr(c, source, pe), nbytes);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    G::sync();
+}
+
+// quiet / fence: the calling thread's outstanding memory operations, then a system-scope release
+// (the second wait is kept: the fence's own may be dropped by the compiler).
+template <typename G>
+__device__ inline void quiet_group()
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    G::sync();
+    if (G::rank() == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    }
+    G::sync();
 }
 
 template <typename T>
@@ -977,5 +1069,97 @@ ISHMEMX_DEV_ARITH_TYPES(ISHMEMX_DEV_TYPED, min, ISHMEMI_OP_MIN)
 ISHMEMX_DEV_ARITH_TYPES(ISHMEMX_DEV_TYPED, sum, ISHMEMI_OP_SUM)
 ISHMEMX_DEV_ARITH_TYPES(ISHMEMX_DEV_TYPED, prod, ISHMEMI_OP_PROD)
 ISHMEMX_DEV_ARITH_TYPES(ISHMEMX_DEV_COLL, _, _)
+
+/* ---- put / get / p / g, quiet / fence from a kernel (src/ishmem.h:90-330, src/ishmemx.h) --------
+ * ishmem_<TN>_put / _get (one work-item; every calling work-item moves its own arguments),
+ * ishmemx_<TN>_put_work_group / _get_work_group (every thread of the group, same arguments), their
+ * _nbi forms (complete eagerly here), sized (8..128) and mem forms, ishmem_<TN>_p / _g (one
+ * system-scope store / load: g is never served from a warm cache line), ishmem_quiet / fence and
+ * ishmemx_quiet_work_group / fence_work_group.  dest of a put / source of a get: symmetric-heap
+ * address.  Visibility on the target: DESIGN.md §3b. */
+#define ISHMEMX_DEV_RMA_GENERIC(NAME, PUT)                                                          \
+    template <typename T>                                                                          \
+    __device__ inline void ishmem_##NAME(T *dest, const T *source, size_t nelems, int pe)          \
+    {                                                                                              \
+        ishmemx_dev::rma_call<ishmemx_dev::thread_t, PUT>((void *) dest, (const void *) source, nelems * sizeof(T), pe); \
+    }                                                                                              \
+    template <typename T, typename Group>                                                          \
+    __device__ inline void ishmemx_##NAME##_work_group(T *dest, const T *source, size_t nelems, int pe, const Group &) \
+    {                                                                                              \
+        ishmemx_dev::rma_call<ishmemx_dev::exec_t<Group>, PUT>((void *) dest, (const void *) source, \
+                                                               nelems * sizeof(T), pe);            \
+    }
+ISHMEMX_DEV_RMA_GENERIC(put, true)
+ISHMEMX_DEV_RMA_GENERIC(get, false)
+ISHMEMX_DEV_RMA_GENERIC(put_nbi, true)
+ISHMEMX_DEV_RMA_GENERIC(get_nbi, false)
+#define ISHMEMX_DEV_RMA_MEM(NAME, PUT, MUL)                                                         \
+    __device__ inline void ishmem_##NAME(void *dest, const void *source, size_t n, int pe)         \
+    {                                                                                              \
+        ishmemx_dev::rma_call<ishmemx_dev::thread_t, PUT>(dest, source, n * (MUL), pe);            \
+    }                                                                                              \
+    template <typename Group>                                                                      \
+    __device__ inline void ishmemx_##NAME##_work_group(void *dest, const void *source, size_t n, int pe, const Group &) \
+    {                                                                                              \
+        ishmemx_dev::rma_call<ishmemx_dev::exec_t<Group>, PUT>(dest, source, n * (MUL), pe);       \
+    }
+#define ISHMEMX_DEV_RMA_MEM_BOTH(SUFFIX, MUL)                                                       \
+    ISHMEMX_DEV_RMA_MEM(put##SUFFIX, true, MUL)                                                     \
+    ISHMEMX_DEV_RMA_MEM(get##SUFFIX, false, MUL)                                                    \
+    ISHMEMX_DEV_RMA_MEM(put##SUFFIX##_nbi, true, MUL)                                               \
+    ISHMEMX_DEV_RMA_MEM(get##SUFFIX##_nbi, false, MUL)
+ISHMEMX_DEV_RMA_MEM_BOTH(mem, 1)
+ISHMEMX_DEV_RMA_MEM_BOTH(8, 1)
+ISHMEMX_DEV_RMA_MEM_BOTH(16, 2)
+ISHMEMX_DEV_RMA_MEM_BOTH(32, 4)
+ISHMEMX_DEV_RMA_MEM_BOTH(64, 8)
+ISHMEMX_DEV_RMA_MEM_BOTH(128, 16)
+template <typename T>
+__device__ inline void ishmem_p(T *dest, T value, int pe)
+{
+    static_assert(sizeof(T) == 1 || sizeof(T) == 2 || sizeof(T) == 4 || sizeof(T) == 8, "ishmem_p: 1, 2, 4 or 8 bytes");
+    const ishmemi_c_device_ctx_t *c = ishmemx_dev::ctx();
+    if (!c || pe < 0 || pe >= c->npes) return;
+    ishmemx_dev::sys_store((T *) ishmemx_dev::peer_addr(c, dest, pe), value);
+}
+template <typename T>
+__device__ inline T ishmem_g(const T *source, int pe)
+{
+    static_assert(sizeof(T) == 1 || sizeof(T) == 2 || sizeof(T) == 4 || sizeof(T) == 8, "ishmem_g: 1, 2, 4 or 8 bytes");
+    const ishmemi_c_device_ctx_t *c = ishmemx_dev::ctx();
+    if (!c || pe < 0 || pe >= c->npes) return T();
+    return ishmemx_dev::sys_load((const T *) ishmemx_dev::peer_addr(c, source, pe));
+}
+#define ISHMEMX_DEV_RMA_TYPED_ONE(TYPENAME, TYPE, NAME)                                             \
+    __device__ inline void ishmem_##TYPENAME##_##NAME(TYPE *d, const TYPE *s, size_t n, int pe)    \
+    {                                                                                              \
+        ishmem_##NAME<TYPE>(d, s, n, pe);                                                          \
+    }                                                                                              \
+    template <typename Group>                                                                      \
+    __device__ inline void ishmemx_##TYPENAME##_##NAME##_work_group(TYPE *d, const TYPE *s, size_t n, int pe, \
+                                                                    const Group &grp)              \
+    {                                                                                              \
+        ishmemx_##NAME##_work_group<TYPE>(d, s, n, pe, grp);                                       \
+    }
+#define ISHMEMX_DEV_RMA_TYPED(TYPENAME, TYPE, UNUSED1, UNUSED2)                                     \
+    ISHMEMX_DEV_RMA_TYPED_ONE(TYPENAME, TYPE, put)                                                  \
+    ISHMEMX_DEV_RMA_TYPED_ONE(TYPENAME, TYPE, get)                                                  \
+    ISHMEMX_DEV_RMA_TYPED_ONE(TYPENAME, TYPE, put_nbi)                                              \
+    ISHMEMX_DEV_RMA_TYPED_ONE(TYPENAME, TYPE, get_nbi)                                              \
+    __device__ inline void ishmem_##TYPENAME##_p(TYPE *d, TYPE v, int pe) { ishmem_p<TYPE>(d, v, pe); } \
+    __device__ inline TYPE ishmem_##TYPENAME##_g(const TYPE *s, int pe) { return ishmem_g<TYPE>(s, pe); }
+ISHMEMX_DEV_ARITH_TYPES(ISHMEMX_DEV_RMA_TYPED, _, _)
+__device__ inline void ishmem_quiet(void) { ishmemx_dev::quiet_group<ishmemx_dev::thread_t>(); }
+__device__ inline void ishmem_fence(void) { ishmemx_dev::quiet_group<ishmemx_dev::thread_t>(); }
+template <typename Group>
+__device__ inline void ishmemx_quiet_work_group(const Group &)
+{
+    ishmemx_dev::quiet_group<ishmemx_dev::exec_t<Group>>();
+}
+template <typename Group>
+__device__ inline void ishmemx_fence_work_group(const Group &)
+{
+    ishmemx_dev::quiet_group<ishmemx_dev::exec_t<Group>>();
+}
 
 #endif /* ISHMEM_AMD_ISHMEMX_DEVICE_H */

@@ -363,6 +363,73 @@ def team_sync_on_stream(team: int, ret: int | None, stream: int) -> int:
     return _L.ishmemi_c_team_sync_on_stream(team, ret or None, stream or None)
 
 
+# ---- put / get, quiet / fence (src/ishmem.h:90-330) ----------------------------
+# Addresses are integers; the remote side (dest of a put, source of a get) is a symmetric-heap
+# address.  Like the C ABI these return 0 / nonzero (the C++ names return void); last_error() has
+# the reason.
+def ishmem_putmem(dest: int, source: int, nbytes: int, pe: int) -> int:
+    return _L.ishmemi_c_put(dest, source, nbytes, pe)
+
+
+def ishmem_getmem(dest: int, source: int, nbytes: int, pe: int) -> int:
+    return _L.ishmemi_c_get(dest, source, nbytes, pe)
+
+
+def ishmem_putmem_nbi(dest: int, source: int, nbytes: int, pe: int) -> int:
+    return _L.ishmemi_c_put_nbi(dest, source, nbytes, pe)
+
+
+def ishmem_getmem_nbi(dest: int, source: int, nbytes: int, pe: int) -> int:
+    return _L.ishmemi_c_get_nbi(dest, source, nbytes, pe)
+
+
+def ishmem_quiet() -> int:
+    """Every _nbi put / get issued so far by this PE is complete."""
+    return _L.ishmemi_c_quiet()
+
+
+def ishmem_fence() -> int:
+    """Nothing to do on the host beyond validity: the _nbi stream is in order."""
+    return _L.ishmemi_c_fence()
+
+
+def _rma_on_stream(fn, dest, source, nbytes, pe, stream, deps, done) -> int:
+    st = stream or None
+    if deps:
+        hs = [_event_handle(e) for e in deps]
+        if _L.ishmemi_c_stream_wait_events(st, (ctypes.c_void_p * len(hs))(*hs), len(hs)):
+            return 1
+    if fn(dest, source, nbytes, pe, st) if fn is not None else _L.ishmemi_c_quiet_on_stream(st):
+        return 1
+    return _L.ishmemi_c_stream_record_event(st, _event_handle(done)) if done is not None else 0
+
+
+def put_on_stream(dest: int, source: int, nbytes: int, pe: int, stream: int, deps=(), done=None) -> int:
+    """ishmemx_putmem_on_queue analogue (the _nbi form is the same call: the stream orders it)."""
+    return _rma_on_stream(_L.ishmemi_c_put_on_stream, dest, source, nbytes, pe, stream, deps, done)
+
+
+def get_on_stream(dest: int, source: int, nbytes: int, pe: int, stream: int, deps=(), done=None) -> int:
+    return _rma_on_stream(_L.ishmemi_c_get_on_stream, dest, source, nbytes, pe, stream, deps, done)
+
+
+def quiet_on_stream(stream: int, deps=(), done=None) -> int:
+    """`stream` waits for every _nbi put / get issued so far (ishmemx_quiet_on_queue)."""
+    return _rma_on_stream(None, 0, 0, 0, 0, stream, deps, done)
+
+
+def _make_rma(put: bool, nbi: bool, size: int):
+    call = {(True, False): _L.ishmemi_c_put, (False, False): _L.ishmemi_c_get,
+            (True, True): _L.ishmemi_c_put_nbi, (False, True): _L.ishmemi_c_get_nbi}[(put, nbi)]
+
+    def fn(dest: int, source: int, nelems: int, pe: int) -> int:
+        return call(dest, source, nelems * size, pe)
+    return fn
+
+
+RMA_NAMES: list[str] = ["ishmem_putmem", "ishmem_getmem", "ishmem_putmem_nbi", "ishmem_getmem_nbi"]
+
+
 def scan(dtype: str, inclusive: bool, dest: int, source: int, nelems: int,
          team: int = ISHMEM_TEAM_WORLD) -> int:
     return _L.ishmemi_c_scan(team, DTYPES[dtype], 1 if inclusive else 0, dest, source, nelems)
@@ -395,7 +462,23 @@ for _tn in ARITH_TYPENAMES:  # the reference's fcollect / collect / scan lists =
         _f = _make_coll(_kind, TYPENAMES[_tn], _SIZES[TYPENAMES[_tn]])
         _f.__name__ = _name
         setattr(_mod, _name, _f)
-del _tn, _kind, _name, _f
+    # put / get and their _nbi forms: the 23 RMA typenames of src/ishmem.h:91-113 are the same list.
+    for _put in (True, False):
+        for _nbi in (False, True):
+            _name = f"ishmem_{_tn}_{'put' if _put else 'get'}{'_nbi' if _nbi else ''}"
+            _f = _make_rma(_put, _nbi, _SIZES[TYPENAMES[_tn]])
+            _f.__name__ = _name
+            setattr(_mod, _name, _f)
+            RMA_NAMES.append(_name)
+for _bits in (8, 16, 32, 64, 128):  # ishmem_put8 .. ishmem_get128 (elements of _bits / 8 bytes)
+    for _put in (True, False):
+        for _nbi in (False, True):
+            _name = f"ishmem_{'put' if _put else 'get'}{_bits}{'_nbi' if _nbi else ''}"
+            _f = _make_rma(_put, _nbi, _bits // 8)
+            _f.__name__ = _name
+            setattr(_mod, _name, _f)
+            RMA_NAMES.append(_name)
+del _tn, _kind, _name, _f, _put, _nbi, _bits
 API_NAMES: list[str] = []
 for _op, _tns in TYPENAMES_FOR_OP.items():
     for _tn in _tns:

@@ -59,6 +59,16 @@ PROTOTYPES = [
     ("ishmemi_c_alltoall", _i, [_i, _vp, _vp, _sz]),
     ("ishmemi_c_alltoall_on_stream", _i, [_i, _vp, _vp, _sz, _vp, _vp]),
     ("ishmemi_c_collect_on_stream", _i, [_i, _vp, _vp, _sz, _vp, _vp]),
+    ("ishmemi_c_put", _i, [_vp, _vp, _sz, _i]),
+    ("ishmemi_c_get", _i, [_vp, _vp, _sz, _i]),
+    ("ishmemi_c_put_nbi", _i, [_vp, _vp, _sz, _i]),
+    ("ishmemi_c_get_nbi", _i, [_vp, _vp, _sz, _i]),
+    ("ishmemi_c_put_on_stream", _i, [_vp, _vp, _sz, _i, _vp]),
+    ("ishmemi_c_get_on_stream", _i, [_vp, _vp, _sz, _i, _vp]),
+    ("ishmemi_c_quiet", _i, []),
+    ("ishmemi_c_fence", _i, []),
+    ("ishmemi_c_quiet_on_stream", _i, [_vp]),
+    ("ishmemi_c_read_all_u32", _i, [_vp, _vp, _sz, _i, _vp]),
     ("ishmemi_c_stream_wait_events", _i, [_vp, _vp, _sz]),
     ("ishmemi_c_stream_record_event", _i, [_vp, _vp]),
     ("ishmemi_c_collect", _i, [_i, _vp, _vp, _sz]),

@@ -308,4 +308,17 @@ int phase_unaligned();
 hipError_t launch_occupy(int grid, uint64_t usec, hipStream_t s);
 hipError_t launch_produce_u32(uint32_t *dst, const uint32_t *a, const uint32_t *b, uint64_t n, hipStream_t s);
 
+// put / get (kernels_rma.hip): `head` bytes up to dst's first 16-B boundary, `nitems` 16-B items,
+// `tail` bytes; one of dst / src is a peer's heap as mapped in this process.  put: remote stores
+// write-through (sc0 sc1); get: remote loads system-coherent.  Grid = tiles of kBlock * kUnroll
+// items, at most max_blocks workgroups (grid-stride beyond that).
+struct RmaArgs {
+    char *dst;
+    const char *src;
+    uint64_t head, nitems, tail;
+};
+hipError_t launch_rma_copy(const RmaArgs &a, bool put, int max_blocks, hipStream_t s);
+// Test hook: `grid` workgroups that each read all n words of p with plain loads into out[b * n ..].
+hipError_t launch_read_all_u32(uint32_t *out, const uint32_t *p, uint64_t n, int grid, hipStream_t s);
+
 }  // namespace ishmemi

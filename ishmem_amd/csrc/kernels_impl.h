@@ -33,9 +33,11 @@
 //     "ready" flag per reduced segment (the RS -> AG hand-off) and one "done reading" flag per
 //     member, exchanged by whichever workgroup gets there; work is grabbed from per-launch
 //     counters, so no workgroup ever waits for a particular peer workgroup and the launch
-//     completes whatever part of the grid is resident.  All remote payload accesses outside the
-//     granule rings are LOADS (pull), so no PE's L2 can hold stale copies of bytes a peer wrote;
-//     the rings are uncached fine-grained memory written and polled with system-scope atomics.
+//     completes whatever part of the grid is resident.  All remote payload accesses of the
+//     COLLECTIVES outside the granule rings are LOADS (pull), so no collective leaves a PE's L2
+//     with stale copies of bytes a peer wrote; the rings are uncached fine-grained memory written
+//     and polled with system-scope atomics.  put (kernels_rma.hip) is the one path that stores
+//     payload into a peer's heap; its visibility contract is DESIGN.md §3b.
 #pragma once
 #include <algorithm>
 #include <map>

@@ -379,6 +379,11 @@ struct State {
     char *staging = nullptr;  // symmetric staging region for non-heap / host buffers
     size_t staging_bytes = 0;
     hipStream_t copy_in = nullptr, copy_out = nullptr;  // staging pipeline streams
+    // put / get _nbi: the library's own non-blocking stream (created by the first _nbi call), in
+    // call order; rma_pending = something was enqueued on it since the last quiet / barrier_all.
+    hipStream_t rma_stream = nullptr;
+    hipEvent_t rma_ev = nullptr;
+    bool rma_pending = false;
     // Stream of the previous collective: a collective enqueued on another stream first waits
     // for it, so epochs, flag rows and the staging region are used in call order.
     hipStream_t last_stream = nullptr;
@@ -1561,6 +1566,82 @@ int alltoall_impl(int team, void *dst, const void *src, size_t nbytes, int *ret,
     return 0;
 }
 
+// ---------------- put / get (ishmem_put / ishmem_get, src/rma.cpp, src/rma_impl.h) ----------------
+// The first calls that STORE payload into a peer's heap (DESIGN.md §3b has the visibility contract).
+// One side is the peer's heap as mapped here (dest of a put, source of a get: given as this PE's
+// symmetric address, inside the heap for its whole length), the other this PE's memory: heap,
+// device or pinned host memory for the kernel (kernels_rma.hip); pageable host memory only for the
+// blocking forms, through hipMemcpy to / from the mapped peer address.  The item width comes from
+// the addresses and the byte count.
+//   blocking  - the kernel on the null stream, then host_wait: on return the local buffer is
+//               reusable and the bytes are in the target's memory (write-through stores);
+//   _nbi      - the kernel on the library's non-blocking stream, in call order; ishmemi_c_quiet
+//               waits for that stream, ishmemi_c_barrier_all drains it with the device;
+//   on_stream - the kernel on the caller's stream.
+enum RmaKind { kRmaBlocking = 0, kRmaNbi = 1, kRmaOnStream = 2 };
+
+// The address a kernel of this device uses for `p` (heap, device, managed or pinned / registered
+// host memory); nullptr for memory it cannot reach (pageable host memory).
+char *device_view(const State &s, const void *p)
+{
+    if (in_heap(s, p)) return (char *) p;
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+        (void) hipGetLastError();
+        return nullptr;
+    }
+    if (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged) return (char *) p;
+    if (attr.type == hipMemoryTypeHost && attr.devicePointer) return (char *) attr.devicePointer;
+    return nullptr;
+}
+
+int rma_impl(bool put, void *dest, const void *source, size_t nbytes, int pe, RmaKind kind, hipStream_t user)
+{
+    const std::string what = std::string(put ? "put" : "get") + (kind == kRmaNbi ? "_nbi" : kind == kRmaOnStream ? "_on_stream" : "");
+    State &s = S();
+    std::lock_guard<std::mutex> lk(s.mu);
+    if (!s.initialized) return fail(what + ": not initialized");
+    if (pe < 0 || pe >= s.npes)
+        return fail(what + ": pe " + std::to_string(pe) + " outside [0, " + std::to_string(s.npes) + ")");
+    if (nbytes == 0) return 0;
+    if (!dest || !source) return fail(what + ": null pointer with nbytes > 0");
+    const char *sym = put ? (const char *) dest : (const char *) source;
+    if (!in_heap(s, sym) || nbytes > (size_t) (s.heap + s.heap_size - sym))
+        return fail(what + (put ? ": dest" : ": source") + " is not inside the symmetric heap for its whole length");
+    char *remote = translate(s, sym, pe);
+    if (!remote) return fail(what + ": heap of PE " + std::to_string(pe) + " not mapped");
+    char *local = device_view(s, put ? source : dest);
+    if (!local) {
+        if (kind != kRmaBlocking)
+            return fail(what + (put ? ": source" : ": dest") + " is not device-accessible (heap, device or pinned host "
+                        "memory; pageable host memory is accepted by the blocking host forms only)");
+        if (put) HIP_TRY(hipMemcpy(remote, source, nbytes, hipMemcpyHostToDevice));
+        else HIP_TRY(hipMemcpy(dest, remote, nbytes, hipMemcpyDeviceToHost));
+        return 0;
+    }
+    RmaArgs a{};
+    a.dst = put ? remote : local;
+    a.src = put ? local : remote;
+    a.head = std::min<uint64_t>(nbytes, (16 - ((uintptr_t) a.dst & 15)) & 15);
+    a.nitems = (nbytes - a.head) / 16;
+    a.tail = nbytes - a.head - a.nitems * 16;
+    hipStream_t st = 0;
+    if (kind == kRmaNbi) {
+        if (!s.rma_stream) HIP_TRY(hipStreamCreateWithFlags(&s.rma_stream, hipStreamNonBlocking));
+        st = s.rma_stream;
+    } else if (kind == kRmaOnStream) {
+        st = user;
+        if (order_stream(s, st)) return 1;
+    }
+    HIP_TRY(launch_rma_copy(a, put, s.max_blocks, st));
+    if (kind == kRmaNbi) {
+        s.rma_pending = true;
+        return 0;
+    }
+    if (kind == kRmaOnStream) return mark_stream(s, st);
+    return host_wait(s, st);
+}
+
 int scan_impl(int team, int dt, int inclusive, void *dst, const void *src, size_t n, int *ret,
               hipStream_t st, bool blocking)
 {
@@ -2505,6 +2586,11 @@ int ishmemi_c_finalize(void)
         }
         s.copy_in = s.copy_out = nullptr;
     }
+    if (s.rma_stream) (void) hipStreamDestroy(s.rma_stream);
+    if (s.rma_ev) (void) hipEventDestroy(s.rma_ev);
+    s.rma_stream = nullptr;
+    s.rma_ev = nullptr;
+    s.rma_pending = false;
     if (s.phase_ev[0])
         for (hipEvent_t &e : s.phase_ev) {
             (void) hipEventDestroy(e);
@@ -2974,8 +3060,87 @@ int ishmemi_c_team_sync_on_stream(int team, int *ret, void *stream)
 int ishmemi_c_barrier_all(void)
 {
     // ishmem_barrier_all = quiet + sync_all: complete all outstanding device work first.
+    // That includes the library's _nbi stream: pending _nbi puts / gets are complete after it, so
+    // the barrier implies quiet at no extra cost (a flag cleared under the lock).
     if (hipDeviceSynchronize() != hipSuccess) return fail("barrier_all: device sync failed");
+    {
+        State &s = S();
+        std::lock_guard<std::mutex> lk(s.mu);
+        s.rma_pending = false;
+    }
     return ishmemi_c_team_sync(ISHMEMI_C_TEAM_WORLD);
+}
+
+int ishmemi_c_read_all_u32(void *out, const void *p, size_t n, int grid, void *stream)
+{
+    if (grid < 1 || grid > 1024 || ((uintptr_t) out | (uintptr_t) p) % 4)
+        return fail("read_all_u32: 1..1024 workgroups and 4-B aligned pointers required");
+    HIP_TRY(launch_read_all_u32((uint32_t *) out, (const uint32_t *) p, n, grid, (hipStream_t) stream));
+    return 0;
+}
+
+int ishmemi_c_put(void *dest, const void *source, size_t nbytes, int pe)
+{
+    return rma_impl(true, dest, source, nbytes, pe, kRmaBlocking, 0);
+}
+
+int ishmemi_c_get(void *dest, const void *source, size_t nbytes, int pe)
+{
+    return rma_impl(false, dest, source, nbytes, pe, kRmaBlocking, 0);
+}
+
+int ishmemi_c_put_nbi(void *dest, const void *source, size_t nbytes, int pe)
+{
+    return rma_impl(true, dest, source, nbytes, pe, kRmaNbi, 0);
+}
+
+int ishmemi_c_get_nbi(void *dest, const void *source, size_t nbytes, int pe)
+{
+    return rma_impl(false, dest, source, nbytes, pe, kRmaNbi, 0);
+}
+
+int ishmemi_c_put_on_stream(void *dest, const void *source, size_t nbytes, int pe, void *stream)
+{
+    return rma_impl(true, dest, source, nbytes, pe, kRmaOnStream, (hipStream_t) stream);
+}
+
+int ishmemi_c_get_on_stream(void *dest, const void *source, size_t nbytes, int pe, void *stream)
+{
+    return rma_impl(false, dest, source, nbytes, pe, kRmaOnStream, (hipStream_t) stream);
+}
+
+int ishmemi_c_quiet(void)
+{
+    State &s = S();
+    std::lock_guard<std::mutex> lk(s.mu);
+    if (!s.initialized) return fail("quiet: not initialized");
+    if (s.rma_pending) {
+        HIP_TRY(hipStreamSynchronize(s.rma_stream));
+        s.rma_pending = false;
+    }
+    return 0;
+}
+
+int ishmemi_c_fence(void)
+{
+    // The _nbi stream is in order: puts to one PE are delivered in call order already.
+    return S().initialized ? 0 : fail("fence: not initialized");
+}
+
+int ishmemi_c_quiet_on_stream(void *stream)
+{
+    State &s = S();
+    std::lock_guard<std::mutex> lk(s.mu);
+    if (!s.initialized) return fail("quiet_on_stream: not initialized");
+    if (!s.rma_pending) return 0;
+    hipStream_t st = (hipStream_t) stream;
+    if (capturing(st))
+        return fail("quiet_on_stream: _nbi operations are pending and the stream is being captured (call ishmem_quiet "
+                    "before the capture)");
+    if (!s.rma_ev) HIP_TRY(hipEventCreateWithFlags(&s.rma_ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(s.rma_ev, s.rma_stream));
+    HIP_TRY(hipStreamWaitEvent(st, s.rma_ev, 0));
+    return 0;
 }
 
 int ishmemi_c_resync(void)
