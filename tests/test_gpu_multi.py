@@ -120,8 +120,10 @@ def test_fcollect_collect_scan_vs_tester_patterns_and_oracle(npes, ll):
 
 @pytest.mark.parametrize("npes", [2, 3])
 def test_scan_collect_on_the_phased_paths(npes):
-    # The threshold forced to 0: at 2 PEs disjoint scans take the direct fold (no scratch), in-place
-    # ones and every scan at 3 PEs the phased segments; fcollect / collect the phased pull grid.
+    # The threshold forced to 0: every scan here has disjoint buffers, so at 2 PEs all take the
+    # direct fold (no scratch) and at 3 PEs those above the fold bound the phased segments;
+    # fcollect / collect the phased pull grid.  In-place scans (scan_kernel and the phased pair at
+    # 2 PEs, and at small shapes) are in tests/test_gpu_coll_edges.py.
     # Tester patterns and seeded inputs vs the oracle, as in the default-path test above.
     run_pes(npes, ["collect", "scan"], env={"ISHMEM_STAGING_SIZE": "4M", "ISHMEM_PHASED_MIN_BYTES": 0,
                                             "ISHMEM_LL_MAX_BYTES": 0}, timeout=300)
