@@ -464,6 +464,120 @@ ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_RMA_TYPED, _, _)
 inline void ishmem_quiet(void) { (void) ishmemi_c_quiet(); }
 inline void ishmem_fence(void) { (void) ishmemi_c_fence(); }
 
+/* ---- put with signal, signal_fetch, wait_until / test (src/ishmem.h:28-36, :640-705, :1320-1354,
+ *      :1551-1552) ------------------------------------------------------------------------------
+ * Host forms; the device-callable forms of the same names are in ishmemx_device.h.  void / value
+ * returning, as in the reference: a failure (a wait that timed out included) leaves its reason in
+ * ishmemi_c_last_error(), and ishmem_signal_wait_until then returns the last value read.  The signal
+ * word is updated on `pe` only after every payload byte is in its memory: DESIGN.md §3c. */
+#define ISHMEM_CMP_EQ ISHMEMI_C_CMP_EQ
+#define ISHMEM_CMP_NE ISHMEMI_C_CMP_NE
+#define ISHMEM_CMP_GT ISHMEMI_C_CMP_GT
+#define ISHMEM_CMP_GE ISHMEMI_C_CMP_GE
+#define ISHMEM_CMP_LT ISHMEMI_C_CMP_LT
+#define ISHMEM_CMP_LE ISHMEMI_C_CMP_LE
+#define ISHMEM_SIGNAL_SET ISHMEMI_C_SIGNAL_SET
+#define ISHMEM_SIGNAL_ADD ISHMEMI_C_SIGNAL_ADD
+
+inline void ishmem_putmem_signal(void *dest, const void *source, size_t nbytes, uint64_t *sig_addr, uint64_t signal,
+                                 int sig_op, int pe)
+{
+    (void) ishmemi_c_put_signal(dest, source, nbytes, sig_addr, signal, sig_op, pe);
+}
+inline void ishmem_putmem_signal_nbi(void *dest, const void *source, size_t nbytes, uint64_t *sig_addr, uint64_t signal,
+                                     int sig_op, int pe)
+{
+    (void) ishmemi_c_put_signal_nbi(dest, source, nbytes, sig_addr, signal, sig_op, pe);
+}
+template <typename T>
+inline void ishmem_put_signal(T *dest, const T *source, size_t nelems, uint64_t *sig_addr, uint64_t signal, int sig_op,
+                              int pe)
+{
+    (void) ishmemi_c_put_signal((void *) dest, (const void *) source, nelems * sizeof(T), sig_addr, signal, sig_op, pe);
+}
+template <typename T>
+inline void ishmem_put_signal_nbi(T *dest, const T *source, size_t nelems, uint64_t *sig_addr, uint64_t signal,
+                                  int sig_op, int pe)
+{
+    (void) ishmemi_c_put_signal_nbi((void *) dest, (const void *) source, nelems * sizeof(T), sig_addr, signal, sig_op, pe);
+}
+#define ISHMEMI_CXX_PUT_SIGNAL_SIZED(BITS)                                                          \
+    inline void ishmem_put##BITS##_signal(void *d, const void *s, size_t n, uint64_t *sig, uint64_t v, int op, int pe) \
+    {                                                                                              \
+        ishmem_putmem_signal(d, s, n * (BITS / 8), sig, v, op, pe);                                \
+    }                                                                                              \
+    inline void ishmem_put##BITS##_signal_nbi(void *d, const void *s, size_t n, uint64_t *sig, uint64_t v, int op, int pe) \
+    {                                                                                              \
+        ishmem_putmem_signal_nbi(d, s, n * (BITS / 8), sig, v, op, pe);                            \
+    }
+ISHMEMI_CXX_PUT_SIGNAL_SIZED(8)
+ISHMEMI_CXX_PUT_SIGNAL_SIZED(16)
+ISHMEMI_CXX_PUT_SIGNAL_SIZED(32)
+ISHMEMI_CXX_PUT_SIGNAL_SIZED(64)
+ISHMEMI_CXX_PUT_SIGNAL_SIZED(128)
+#define ISHMEMI_CXX_PUT_SIGNAL_TYPED(TYPENAME, TYPE, UNUSED1, UNUSED2)                              \
+    inline void ishmem_##TYPENAME##_put_signal(TYPE *d, const TYPE *s, size_t n, uint64_t *sig, uint64_t v, int op, int pe) \
+    {                                                                                              \
+        ishmem_put_signal(d, s, n, sig, v, op, pe);                                                \
+    }                                                                                              \
+    inline void ishmem_##TYPENAME##_put_signal_nbi(TYPE *d, const TYPE *s, size_t n, uint64_t *sig, uint64_t v, int op, \
+                                                   int pe)                                         \
+    {                                                                                              \
+        ishmem_put_signal_nbi(d, s, n, sig, v, op, pe);                                            \
+    }
+ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_PUT_SIGNAL_TYPED, _, _)
+
+inline uint64_t ishmem_signal_fetch(uint64_t *sig_addr)
+{
+    uint64_t v = 0;
+    (void) ishmemi_c_signal_fetch(sig_addr, &v);
+    return v;
+}
+inline uint64_t ishmem_signal_wait_until(uint64_t *sig_addr, int cmp, uint64_t cmp_value)
+{
+    uint64_t v = 0;
+    (void) ishmemi_c_wait_until((void *) sig_addr, ISHMEMI_DT_UINT64, cmp, cmp_value, &v);
+    return v;
+}
+
+namespace ishmemi_cxx {
+/* The synchronisation types: 32- and 64-bit integers, compared in their own type. */
+template <typename T>
+constexpr int sync_dtype()
+{
+    static_assert(std::is_integral<T>::value && (sizeof(T) == 4 || sizeof(T) == 8),
+                  "wait_until / test: a 32- or 64-bit integer type");
+    return std::is_signed<T>::value ? (sizeof(T) == 4 ? ISHMEMI_DT_INT32 : ISHMEMI_DT_INT64)
+                                    : (sizeof(T) == 4 ? ISHMEMI_DT_UINT32 : ISHMEMI_DT_UINT64);
+}
+template <typename T>
+constexpr uint64_t sync_bits(T v)
+{
+    return (uint64_t) (typename std::make_unsigned<T>::type) v;
+}
+}  // namespace ishmemi_cxx
+template <typename T>
+inline void ishmem_wait_until(T *ivar, int cmp, T cmp_value)
+{
+    (void) ishmemi_c_wait_until((void *) ivar, ishmemi_cxx::sync_dtype<T>(), cmp, ishmemi_cxx::sync_bits(cmp_value), nullptr);
+}
+template <typename T>
+inline int ishmem_test(T *ivar, int cmp, T cmp_value)
+{
+    int r = 0;
+    (void) ishmemi_c_test((void *) ivar, ishmemi_cxx::sync_dtype<T>(), cmp, ishmemi_cxx::sync_bits(cmp_value), &r);
+    return r;
+}
+/* The 12 synchronisation typenames (src/ishmem.h:1320-1354). */
+#define ISHMEMI_CXX_SYNC_TYPES(X)                                                                   \
+    X(int, int) X(long, long) X(longlong, long long) X(uint, unsigned int) X(ulong, unsigned long)  \
+    X(ulonglong, unsigned long long) X(int32, int32_t) X(int64, int64_t) X(uint32, uint32_t)        \
+    X(uint64, uint64_t) X(size, size_t) X(ptrdiff, ptrdiff_t)
+#define ISHMEMI_CXX_SYNC_TYPED(TYPENAME, TYPE)                                                      \
+    inline void ishmem_##TYPENAME##_wait_until(TYPE *ivar, int cmp, TYPE v) { ishmem_wait_until<TYPE>(ivar, cmp, v); } \
+    inline int ishmem_##TYPENAME##_test(TYPE *ivar, int cmp, TYPE v) { return ishmem_test<TYPE>(ivar, cmp, v); }
+ISHMEMI_CXX_SYNC_TYPES(ISHMEMI_CXX_SYNC_TYPED)
+
 /* Compiled as HIP: the device-callable half of this API (the reference's SYCL_EXTERNAL functions:
  * ishmem_my_pe / ishmem_<TN>_<op>_reduce / ... from inside a kernel, ishmemx_*_work_group). */
 #if defined(__HIP__)

@@ -278,6 +278,52 @@ int ishmemi_c_quiet_on_stream(void *stream);
  * lines; after, it shows what plain loads see there.  Asynchronous on `stream`. */
 int ishmemi_c_read_all_u32(void *out, const void *p, size_t n, int grid, void *stream);
 
+/* ---- put with signal, signal operations, wait_until / test — ishmem_put_signal / ishmemx_signal_set /
+ *      ishmemx_signal_add / ishmem_signal_fetch / ishmem_signal_wait_until / ishmem_<TN>_wait_until /
+ *      ishmem_<TN>_test (src/ishmem.h:640-705, :1320-1354, :1551-1552, src/signaling.cpp,
+ *      src/synchronization.cpp) ----------------------------------------------------------------------
+ * put_signal: `nbytes` from `source` into `dest` on `pe` as ishmemi_c_put does, then the uint64_t at
+ * `sig` on `pe` (this PE's symmetric address, 8-byte aligned, inside the heap) is updated:
+ * sig_op ISHMEMI_C_SIGNAL_SET = atomic store of `value`, ISHMEMI_C_SIGNAL_ADD = atomic add.  The
+ * update becomes visible on the target only after every payload byte is in its memory.  nbytes == 0
+ * still updates the signal; pe == my_pe is legal.  The blocking, _nbi and _on_stream forms go where
+ * put's go (quiet / barrier_all cover _nbi); pageable source: the blocking form only.
+ *   signal_op     the signal update alone (ishmemx_signal_set / ishmemx_signal_add), blocking;
+ *   signal_fetch  *value = this PE's signal word, read from memory;
+ *   wait_until    blocks until the variable `ivar` of this PE (symmetric address, aligned to its
+ *                 width; `dtype` one of ISHMEMI_DT_INT32 / UINT32 / INT64 / UINT64) compares `cmp`
+ *                 (ISHMEMI_C_CMP_EQ .. LE, in the variable's own type) against `cmp_value_bits` (the
+ *                 value's bits, zero-extended); *value (may be null) = the value that satisfied it,
+ *                 zero- or sign-extended.  ishmem_signal_wait_until is dtype UINT64;
+ *   test          *result = 1 if the comparison holds now, else 0;
+ *   wait_until_on_stream  the wait enqueued on `stream`; *value (device-accessible, may be null) as
+ *                 above; *ret (device-accessible, may be null) = 0, or nonzero if the wait timed out.
+ *                 Capturable; it is not ordered against other streams' calls by "stream_order".
+ * Every wait is bounded by "timeout_ms": a host wait that times out returns nonzero, leaves the last
+ * value read in *value and raises ishmemi_c_error_count.  The blocking waits run on library streams
+ * of their own (never the null stream) and do not hold the library's lock while they wait.
+ * Argument errors (pe, sig_op, cmp, dtype, alignment, address outside the heap, null pointer) return
+ * nonzero before anything is launched and do not move ishmemi_c_error_count.  Contract: DESIGN.md §3c. */
+#define ISHMEMI_C_SIGNAL_SET 0
+#define ISHMEMI_C_SIGNAL_ADD 1
+#define ISHMEMI_C_CMP_EQ 1
+#define ISHMEMI_C_CMP_NE 2
+#define ISHMEMI_C_CMP_GT 3
+#define ISHMEMI_C_CMP_GE 4
+#define ISHMEMI_C_CMP_LT 5
+#define ISHMEMI_C_CMP_LE 6
+int ishmemi_c_put_signal(void *dest, const void *source, size_t nbytes, uint64_t *sig, uint64_t value, int sig_op, int pe);
+int ishmemi_c_put_signal_nbi(void *dest, const void *source, size_t nbytes, uint64_t *sig, uint64_t value, int sig_op,
+                             int pe);
+int ishmemi_c_put_signal_on_stream(void *dest, const void *source, size_t nbytes, uint64_t *sig, uint64_t value,
+                                   int sig_op, int pe, void *stream);
+int ishmemi_c_signal_op(uint64_t *sig, uint64_t value, int sig_op, int pe);
+int ishmemi_c_signal_fetch(uint64_t *sig, uint64_t *value);
+int ishmemi_c_wait_until(void *ivar, int dtype, int cmp, uint64_t cmp_value_bits, uint64_t *value);
+int ishmemi_c_test(void *ivar, int dtype, int cmp, uint64_t cmp_value_bits, int *result);
+int ishmemi_c_wait_until_on_stream(void *ivar, int dtype, int cmp, uint64_t cmp_value_bits, uint64_t *value, int *ret,
+                                   void *stream);
+
 /* ---- device-initiated collectives ----------------------------------------------------------
  * The reference's device-callable reductions (ishmemx_<TN>_<op>_reduce_work_group,
  * src/collectives/reduce_impl.h:386-418, :505-518, src/ishmemx.h:1648-1699) read the library
@@ -337,7 +383,10 @@ int ishmemi_c_register_device_ctx_slot(const void *host_shadow);
  * items), "block_spin" (blocking calls' wait: 2, default, spin on a stream-written host word; 1 the
  * spin then hipStreamSynchronize; 0 hipStreamSynchronize), "direct_max_pes" (largest team taking
  * the whole-array fold, default 4), "direct_inplace" (1, default: in-place calls with p * B <= 4 MiB
- * fold into the team's private scratch, allocated with the team, and copy back).  The thresholds
+ * fold into the team's private scratch, allocated with the team, and copy back),
+ * "put_signal_fused_max_bytes" (put_signal payloads up to this size take the fused one-workgroup
+ * kernel, larger ones the put grid and a signal kernel; default 32768, ISHMEM_PUT_SIGNAL_FUSED_MAX_BYTES;
+ * chosen by the origin alone, may differ between PEs).  The thresholds
  * choose the kernels of a multi-PE call: init agrees on them (the minimum over the PEs; the
  * maximum for "phased_min_bytes") and a later set_param must be made with the same value on every
  * PE.  "max_blocks" may differ between PEs (the kernels grab work, nothing is paired by workgroup

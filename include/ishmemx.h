@@ -441,6 +441,123 @@ inline int ishmemx_quiet_on_stream(hipStream_t stream, const hipEvent_t *deps, s
     return ishmemi_cxx::with_events(stream, deps, ndeps, done, [&] { return ishmemi_c_quiet_on_stream((void *) stream); });
 }
 
+/* Signal operations (ishmemx_signal_set / ishmemx_signal_add, src/ishmemx.h:733-735): one atomic on
+ * `pe`'s signal word, blocking. */
+inline void ishmemx_signal_set(uint64_t *sig_addr, uint64_t signal, int pe)
+{
+    (void) ishmemi_c_signal_op(sig_addr, signal, ISHMEM_SIGNAL_SET, pe);
+}
+inline void ishmemx_signal_add(uint64_t *sig_addr, uint64_t signal, int pe)
+{
+    (void) ishmemi_c_signal_op(sig_addr, signal, ISHMEM_SIGNAL_ADD, pe);
+}
+
+/* put with signal on a stream (ishmemx_*_put_signal[_nbi]_on_queue, src/ishmemx.h:608-738): enqueued
+ * on `stream`, which orders it, so the _nbi form coincides with the plain one. */
+#define ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_MEM(NAME, MUL)                                             \
+    inline int ishmemx_##NAME##_on_stream(void *dest, const void *source, size_t n, uint64_t *sig, uint64_t v, int op, \
+                                          int pe, hipStream_t stream)                              \
+    {                                                                                              \
+        return ishmemi_c_put_signal_on_stream(dest, source, n * (MUL), sig, v, op, pe, (void *) stream); \
+    }                                                                                              \
+    inline int ishmemx_##NAME##_on_stream(void *dest, const void *source, size_t n, uint64_t *sig, uint64_t v, int op, \
+                                          int pe, hipStream_t stream, const hipEvent_t *deps, size_t ndeps,      \
+                                          hipEvent_t done)                                         \
+    {                                                                                              \
+        return ishmemi_cxx::with_events(stream, deps, ndeps, done, [&] {                           \
+            return ishmemi_c_put_signal_on_stream(dest, source, n * (MUL), sig, v, op, pe, (void *) stream); \
+        });                                                                                        \
+    }
+#define ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_BOTH(SUFFIX, MUL)                                          \
+    ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_MEM(put##SUFFIX##_signal, MUL)                                 \
+    ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_MEM(put##SUFFIX##_signal_nbi, MUL)
+ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_BOTH(mem, 1)
+ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_BOTH(8, 1)
+ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_BOTH(16, 2)
+ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_BOTH(32, 4)
+ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_BOTH(64, 8)
+ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_BOTH(128, 16)
+#define ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_T(NAME)                                                    \
+    template <typename T>                                                                          \
+    inline int ishmemx_##NAME##_on_stream(T *dest, const T *source, size_t nelems, uint64_t *sig, uint64_t v, int op, \
+                                          int pe, hipStream_t stream)                              \
+    {                                                                                              \
+        return ishmemi_c_put_signal_on_stream((void *) dest, (const void *) source, nelems * sizeof(T), sig, v, op, pe, \
+                                              (void *) stream);                                    \
+    }                                                                                              \
+    template <typename T>                                                                          \
+    inline int ishmemx_##NAME##_on_stream(T *dest, const T *source, size_t nelems, uint64_t *sig, uint64_t v, int op, \
+                                          int pe, hipStream_t stream, const hipEvent_t *deps, size_t ndeps,      \
+                                          hipEvent_t done)                                         \
+    {                                                                                              \
+        return ishmemi_cxx::with_events(stream, deps, ndeps, done, [&] {                           \
+            return ishmemi_c_put_signal_on_stream((void *) dest, (const void *) source, nelems * sizeof(T), sig, v, op, \
+                                                  pe, (void *) stream);                            \
+        });                                                                                        \
+    }
+ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_T(put_signal)
+ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_T(put_signal_nbi)
+#define ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_TYPED_ONE(TYPENAME, TYPE, NAME)                            \
+    inline int ishmemx_##TYPENAME##_##NAME##_on_stream(TYPE *d, const TYPE *s, size_t n, uint64_t *sig, uint64_t v,    \
+                                                       int op, int pe, hipStream_t st)             \
+    {                                                                                              \
+        return ishmemx_##NAME##_on_stream<TYPE>(d, s, n, sig, v, op, pe, st);                      \
+    }                                                                                              \
+    inline int ishmemx_##TYPENAME##_##NAME##_on_stream(TYPE *d, const TYPE *s, size_t n, uint64_t *sig, uint64_t v,    \
+                                                       int op, int pe, hipStream_t st, const hipEvent_t *deps,   \
+                                                       size_t ndeps, hipEvent_t done)              \
+    {                                                                                              \
+        return ishmemx_##NAME##_on_stream<TYPE>(d, s, n, sig, v, op, pe, st, deps, ndeps, done);   \
+    }
+#define ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_TYPED(TYPENAME, TYPE, UNUSED1, UNUSED2)                    \
+    ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_TYPED_ONE(TYPENAME, TYPE, put_signal)                          \
+    ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_TYPED_ONE(TYPENAME, TYPE, put_signal_nbi)
+ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_PUT_SIGNAL_ON_STREAM_TYPED, _, _)
+
+/* Waits on a stream (ishmemx_<TN>_wait_until_on_queue, ishmemx_signal_wait_until_on_queue,
+ * src/ishmemx.h:2011-2040, :2221-2222): `stream` waits until the variable compares true, bounded by
+ * the library's timeout.  *ret_value (device-accessible, may be null) receives the value that
+ * satisfied the comparison.  Capturable into a graph: the poll target and the compare value are the
+ * kernel's frozen arguments.  A timed-out wait shows in ishmemi_c_error_count() (and in `*ret` of
+ * ishmemi_c_wait_until_on_stream). */
+inline int ishmemx_signal_wait_until_on_stream(uint64_t *sig_addr, int cmp, uint64_t cmp_value, uint64_t *ret_value,
+                                               hipStream_t stream)
+{
+    return ishmemi_c_wait_until_on_stream((void *) sig_addr, ISHMEMI_DT_UINT64, cmp, cmp_value, ret_value, nullptr,
+                                          (void *) stream);
+}
+inline int ishmemx_signal_wait_until_on_stream(uint64_t *sig_addr, int cmp, uint64_t cmp_value, uint64_t *ret_value,
+                                               hipStream_t stream, const hipEvent_t *deps, size_t ndeps, hipEvent_t done)
+{
+    return ishmemi_cxx::with_events(stream, deps, ndeps, done, [&] {
+        return ishmemx_signal_wait_until_on_stream(sig_addr, cmp, cmp_value, ret_value, stream);
+    });
+}
+template <typename T>
+inline int ishmemx_wait_until_on_stream(T *ivar, int cmp, T cmp_value, hipStream_t stream)
+{
+    return ishmemi_c_wait_until_on_stream((void *) ivar, ishmemi_cxx::sync_dtype<T>(), cmp, ishmemi_cxx::sync_bits(cmp_value),
+                                          nullptr, nullptr, (void *) stream);
+}
+template <typename T>
+inline int ishmemx_wait_until_on_stream(T *ivar, int cmp, T cmp_value, hipStream_t stream, const hipEvent_t *deps,
+                                        size_t ndeps, hipEvent_t done)
+{
+    return ishmemi_cxx::with_events(stream, deps, ndeps, done,
+                                    [&] { return ishmemx_wait_until_on_stream<T>(ivar, cmp, cmp_value, stream); });
+}
+#define ISHMEMI_CXX_SYNC_ON_STREAM_TYPED(TYPENAME, TYPE)                                            \
+    inline int ishmemx_##TYPENAME##_wait_until_on_stream(TYPE *ivar, int cmp, TYPE v, hipStream_t st) \
+    {                                                                                              \
+        return ishmemx_wait_until_on_stream<TYPE>(ivar, cmp, v, st);                               \
+    }                                                                                              \
+    inline int ishmemx_##TYPENAME##_wait_until_on_stream(TYPE *ivar, int cmp, TYPE v, hipStream_t st,                \
+                                                         const hipEvent_t *deps, size_t ndeps, hipEvent_t done)     \
+    {                                                                                              \
+        return ishmemx_wait_until_on_stream<TYPE>(ivar, cmp, v, st, deps, ndeps, done);            \
+    }
+ISHMEMI_CXX_SYNC_TYPES(ISHMEMI_CXX_SYNC_ON_STREAM_TYPED)
+
 /* Explicit-identity init (the role of ishmemx_init_attr, src/ishmemx.h:21-37). */
 inline int ishmemx_init_pe(int pe, int npes, int device, const char *bootstrap_key)
 {

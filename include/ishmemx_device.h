@@ -10,6 +10,8 @@
  *   fcollect / collect / alltoall / sum_inscan / sum_exscan / broadcast in the same forms;
  *   ishmem_<TYPENAME>_put / _get / _p / _g, their _nbi, sized and mem forms from any work-item,
  *       ishmemx_*_{put,get}[_nbi]_work_group, ishmem_quiet / fence, ishmemx_quiet / fence_work_group;
+ *   ishmem_<TYPENAME>_put_signal[_nbi], ishmemx_*_put_signal[_nbi]_work_group, ishmemx_signal_set / add,
+ *       ishmem_signal_fetch / signal_wait_until, ishmem_<TYPENAME>_wait_until / _test and *_work_group;
  *   ishmem_my_pe / n_pes / team_my_pe / team_n_pes / team_translate_pe / ptr / info_get_*,
  *   ishmem_barrier_all / sync_all / team_sync and their *_work_group forms, ishmemx_print.
  * `grp` is a HIP cooperative group — cooperative_groups::thread_block (the reference's
@@ -659,6 +661,114 @@ __device__ inline void quiet_group()
     G::sync();
 }
 
+// ---- put with signal, wait_until / test from inside a kernel ------------------
+// Bits of the device-API error word (c->err) beside the barrier phases' bits 0-3.
+constexpr uint32_t kErrWaitTimeout = 1u << 8, kErrBadArgument = 1u << 9;
+
+__device__ __forceinline__ void record_error(const ishmemi_c_device_ctx_t *c, uint32_t bit)
+{
+    __hip_atomic_fetch_or(c->err, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// The payload as rma_call<G, true> moves it; EVERY lane then waits for its stores (write-through:
+// acknowledged once the target's memory has them), the group meets, and only then the leader updates
+// the signal word on the target with one system-scope atomic; the group meets again, so no lane
+// returns before the signal is issued.
+template <typename G>
+__device__ inline void put_signal_call(void *dest, const void *source, size_t nbytes, uint64_t *sig_addr, uint64_t signal,
+                                       int sig_op, int pe)
+{
+    const ishmemi_c_device_ctx_t *c = ctx();
+    if (!c || pe < 0 || pe >= c->npes) return;
+    if (sig_op != ISHMEMI_C_SIGNAL_SET && sig_op != ISHMEMI_C_SIGNAL_ADD) {
+        if (G::rank() == 0) record_error(c, kErrBadArgument);
+        return;
+    }
+    G::sync();
+    if (nbytes) rma_group<G, true>(peer_addr(c, dest, pe), (const char *) source, nbytes);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    G::sync();
+    if (G::rank() == 0) {
+        uint64_t *rsig = (uint64_t *) peer_addr(c, sig_addr, pe);
+        if (sig_op == ISHMEMI_C_SIGNAL_ADD)
+            (void) __hip_atomic_fetch_add(rsig, signal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        else __hip_atomic_store(rsig, signal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    G::sync();
+}
+
+__device__ inline void signal_op_call(uint64_t *sig_addr, uint64_t signal, int sig_op, int pe)
+{
+    const ishmemi_c_device_ctx_t *c = ctx();
+    if (!c || pe < 0 || pe >= c->npes) return;
+    uint64_t *rsig = (uint64_t *) peer_addr(c, sig_addr, pe);
+    if (sig_op == ISHMEMI_C_SIGNAL_ADD) (void) __hip_atomic_fetch_add(rsig, signal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    else __hip_atomic_store(rsig, signal, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// ISHMEM_CMP_* in the variable's own type.
+template <typename T>
+__device__ __forceinline__ bool sync_compare(T v, int cmp, T c)
+{
+    switch (cmp) {
+        case ISHMEMI_C_CMP_EQ: return v == c;
+        case ISHMEMI_C_CMP_NE: return v != c;
+        case ISHMEMI_C_CMP_GT: return v > c;
+        case ISHMEMI_C_CMP_GE: return v >= c;
+        case ISHMEMI_C_CMP_LT: return v < c;
+        default: return v <= c;
+    }
+}
+
+// wait_until (budget 0) / test (budget 1) by the group G.  The leader polls the variable relaxed at
+// system scope with a bounded back-off (s_sleep 1 for 32 polls, then 8; the clock every 16 polls).
+// After the match ONE system-scope acquire, and the leader waits for its invalidate BEFORE the
+// group's barrier inside bcast (as group_barrier does), so every wave's plain loads of the bytes the
+// signal announces land behind it.  Returns the value read; *matched = 1 / 0.  A timeout or an
+// invalid cmp is recorded in the device-API error word and returns with *matched = 0.
+template <typename G, typename T>
+__device__ inline T wait_until_group(T *ivar, int cmp, T cmp_value, uint32_t budget, int *matched)
+{
+    static_assert(std::is_integral_v<T> && (sizeof(T) == 4 || sizeof(T) == 8), "wait_until / test: 32- or 64-bit integers");
+    using U = std::conditional_t<sizeof(T) == 8, uint64_t, uint32_t>;
+    const ishmemi_c_device_ctx_t *c = ctx();
+    uint64_t bits = 0;
+    uint32_t ok = 0;
+    if (c && G::rank() == 0) {
+        if (cmp < ISHMEMI_C_CMP_EQ || cmp > ISHMEMI_C_CMP_LE) {
+            record_error(c, kErrBadArgument);
+        } else {
+            const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+            for (uint32_t it = 0;; ++it) {
+                const U u = __hip_atomic_load((const U *) ivar, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                bits = u;
+                if (sync_compare<T>((T) u, cmp, cmp_value)) {
+                    ok = 1;
+                    break;
+                }
+                if (budget && it + 1 >= budget) break;
+                if ((it & 15) == 15 && __builtin_amdgcn_s_memrealtime() - t0 > c->timeout_ticks) {
+                    record_error(c, kErrWaitTimeout);
+                    break;
+                }
+                if (it < 32) __builtin_amdgcn_s_sleep(1);
+                else __builtin_amdgcn_s_sleep(8);
+            }
+            if (ok) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+        }
+    }
+    if constexpr (!std::is_same_v<G, thread_t>) {
+        const uint32_t lo = G::bcast((uint32_t) bits), hi = sizeof(T) == 8 ? G::bcast((uint32_t) (bits >> 32)) : 0u;
+        bits = ((uint64_t) hi << 32) | lo;
+        ok = G::bcast(ok);
+    }
+    if (matched) *matched = (int) ok;
+    return (T) (U) bits;
+}
+
 template <typename T>
 constexpr bool is_canon()
 {
@@ -1161,5 +1271,131 @@ __device__ inline void ishmemx_fence_work_group(const Group &)
 {
     ishmemx_dev::quiet_group<ishmemx_dev::exec_t<Group>>();
 }
+
+/* ---- put with signal, signal operations, wait_until / test from a kernel (src/ishmem.h:640-705,
+ *      :1320-1354, :1551-1552, src/ishmemx.h:608-738, :1906-1920, :2011-2040, :2221-2226) ------------
+ * ishmem_<TN>_put_signal[_nbi] (one work-item), ishmemx_<TN>_put_signal[_nbi]_work_group (a thread
+ * block or a 64-lane tile, same arguments in every thread), sized and mem forms; ishmemx_signal_set /
+ * _add; ishmem_signal_fetch; ishmem_signal_wait_until, ishmem_<TN>_wait_until / _test and their
+ * _work_group forms for the 12 synchronisation typenames.  After a wait (or a test that returned 1)
+ * plain loads of the bytes the signal announced see them.  Every wait is bounded by the library's
+ * timeout; a timed-out wait returns (signal_wait_until: the last value read) and shows in
+ * ishmemi_c_error_count().  DESIGN.md §3c. */
+#define ISHMEMX_DEV_PUT_SIGNAL_GENERIC(NAME)                                                        \
+    template <typename T>                                                                          \
+    __device__ inline void ishmem_##NAME(T *dest, const T *source, size_t nelems, uint64_t *sig_addr, uint64_t signal, \
+                                         int sig_op, int pe)                                       \
+    {                                                                                              \
+        ishmemx_dev::put_signal_call<ishmemx_dev::thread_t>((void *) dest, (const void *) source, nelems * sizeof(T), \
+                                                            sig_addr, signal, sig_op, pe);         \
+    }                                                                                              \
+    template <typename T, typename Group>                                                          \
+    __device__ inline void ishmemx_##NAME##_work_group(T *dest, const T *source, size_t nelems, uint64_t *sig_addr,    \
+                                                       uint64_t signal, int sig_op, int pe, const Group &)       \
+    {                                                                                              \
+        ishmemx_dev::put_signal_call<ishmemx_dev::exec_t<Group>>((void *) dest, (const void *) source,           \
+                                                                 nelems * sizeof(T), sig_addr, signal, sig_op, pe); \
+    }
+ISHMEMX_DEV_PUT_SIGNAL_GENERIC(put_signal)
+ISHMEMX_DEV_PUT_SIGNAL_GENERIC(put_signal_nbi)
+#define ISHMEMX_DEV_PUT_SIGNAL_MEM(NAME, MUL)                                                       \
+    __device__ inline void ishmem_##NAME(void *dest, const void *source, size_t n, uint64_t *sig_addr, uint64_t signal, \
+                                         int sig_op, int pe)                                       \
+    {                                                                                              \
+        ishmemx_dev::put_signal_call<ishmemx_dev::thread_t>(dest, source, n * (MUL), sig_addr, signal, sig_op, pe); \
+    }                                                                                              \
+    template <typename Group>                                                                      \
+    __device__ inline void ishmemx_##NAME##_work_group(void *dest, const void *source, size_t n, uint64_t *sig_addr,   \
+                                                       uint64_t signal, int sig_op, int pe, const Group &)       \
+    {                                                                                              \
+        ishmemx_dev::put_signal_call<ishmemx_dev::exec_t<Group>>(dest, source, n * (MUL), sig_addr, signal, sig_op, pe); \
+    }
+#define ISHMEMX_DEV_PUT_SIGNAL_MEM_BOTH(SUFFIX, MUL)                                                \
+    ISHMEMX_DEV_PUT_SIGNAL_MEM(put##SUFFIX##_signal, MUL)                                           \
+    ISHMEMX_DEV_PUT_SIGNAL_MEM(put##SUFFIX##_signal_nbi, MUL)
+ISHMEMX_DEV_PUT_SIGNAL_MEM_BOTH(mem, 1)
+ISHMEMX_DEV_PUT_SIGNAL_MEM_BOTH(8, 1)
+ISHMEMX_DEV_PUT_SIGNAL_MEM_BOTH(16, 2)
+ISHMEMX_DEV_PUT_SIGNAL_MEM_BOTH(32, 4)
+ISHMEMX_DEV_PUT_SIGNAL_MEM_BOTH(64, 8)
+ISHMEMX_DEV_PUT_SIGNAL_MEM_BOTH(128, 16)
+#define ISHMEMX_DEV_PUT_SIGNAL_TYPED_ONE(TYPENAME, TYPE, NAME)                                      \
+    __device__ inline void ishmem_##TYPENAME##_##NAME(TYPE *d, const TYPE *s, size_t n, uint64_t *sig, uint64_t v,     \
+                                                      int op, int pe)                              \
+    {                                                                                              \
+        ishmem_##NAME<TYPE>(d, s, n, sig, v, op, pe);                                              \
+    }                                                                                              \
+    template <typename Group>                                                                      \
+    __device__ inline void ishmemx_##TYPENAME##_##NAME##_work_group(TYPE *d, const TYPE *s, size_t n, uint64_t *sig,   \
+                                                                    uint64_t v, int op, int pe, const Group &grp) \
+    {                                                                                              \
+        ishmemx_##NAME##_work_group<TYPE>(d, s, n, sig, v, op, pe, grp);                           \
+    }
+#define ISHMEMX_DEV_PUT_SIGNAL_TYPED(TYPENAME, TYPE, UNUSED1, UNUSED2)                              \
+    ISHMEMX_DEV_PUT_SIGNAL_TYPED_ONE(TYPENAME, TYPE, put_signal)                                    \
+    ISHMEMX_DEV_PUT_SIGNAL_TYPED_ONE(TYPENAME, TYPE, put_signal_nbi)
+ISHMEMX_DEV_ARITH_TYPES(ISHMEMX_DEV_PUT_SIGNAL_TYPED, _, _)
+
+__device__ inline void ishmemx_signal_set(uint64_t *sig_addr, uint64_t signal, int pe)
+{
+    ishmemx_dev::signal_op_call(sig_addr, signal, ISHMEMI_C_SIGNAL_SET, pe);
+}
+__device__ inline void ishmemx_signal_add(uint64_t *sig_addr, uint64_t signal, int pe)
+{
+    ishmemx_dev::signal_op_call(sig_addr, signal, ISHMEMI_C_SIGNAL_ADD, pe);
+}
+__device__ inline uint64_t ishmem_signal_fetch(uint64_t *sig_addr) { return ishmemx_dev::sys_load(sig_addr); }
+__device__ inline uint64_t ishmem_signal_wait_until(uint64_t *sig_addr, int cmp, uint64_t cmp_value)
+{
+    return ishmemx_dev::wait_until_group<ishmemx_dev::thread_t, uint64_t>(sig_addr, cmp, cmp_value, 0, nullptr);
+}
+template <typename Group>
+__device__ inline uint64_t ishmemx_signal_wait_until_work_group(uint64_t *sig_addr, int cmp, uint64_t cmp_value,
+                                                                const Group &)
+{
+    return ishmemx_dev::wait_until_group<ishmemx_dev::exec_t<Group>, uint64_t>(sig_addr, cmp, cmp_value, 0, nullptr);
+}
+template <typename T>
+__device__ inline void ishmem_wait_until(T *ivar, int cmp, T cmp_value)
+{
+    (void) ishmemx_dev::wait_until_group<ishmemx_dev::thread_t, T>(ivar, cmp, cmp_value, 0, nullptr);
+}
+template <typename T>
+__device__ inline int ishmem_test(T *ivar, int cmp, T cmp_value)
+{
+    int m = 0;
+    (void) ishmemx_dev::wait_until_group<ishmemx_dev::thread_t, T>(ivar, cmp, cmp_value, 1, &m);
+    return m;
+}
+template <typename T, typename Group>
+__device__ inline void ishmemx_wait_until_work_group(T *ivar, int cmp, T cmp_value, const Group &)
+{
+    (void) ishmemx_dev::wait_until_group<ishmemx_dev::exec_t<Group>, T>(ivar, cmp, cmp_value, 0, nullptr);
+}
+template <typename T, typename Group>
+__device__ inline int ishmemx_test_work_group(T *ivar, int cmp, T cmp_value, const Group &)
+{
+    int m = 0;
+    (void) ishmemx_dev::wait_until_group<ishmemx_dev::exec_t<Group>, T>(ivar, cmp, cmp_value, 1, &m);
+    return m;
+}
+#define ISHMEMX_DEV_SYNC_TYPES(X)                                                                   \
+    X(int, int) X(long, long) X(longlong, long long) X(uint, unsigned int) X(ulong, unsigned long)  \
+    X(ulonglong, unsigned long long) X(int32, int32_t) X(int64, int64_t) X(uint32, uint32_t)        \
+    X(uint64, uint64_t) X(size, size_t) X(ptrdiff, ptrdiff_t)
+#define ISHMEMX_DEV_SYNC_TYPED(TYPENAME, TYPE)                                                      \
+    __device__ inline void ishmem_##TYPENAME##_wait_until(TYPE *ivar, int cmp, TYPE v) { ishmem_wait_until<TYPE>(ivar, cmp, v); } \
+    __device__ inline int ishmem_##TYPENAME##_test(TYPE *ivar, int cmp, TYPE v) { return ishmem_test<TYPE>(ivar, cmp, v); } \
+    template <typename Group>                                                                      \
+    __device__ inline void ishmemx_##TYPENAME##_wait_until_work_group(TYPE *ivar, int cmp, TYPE v, const Group &grp)   \
+    {                                                                                              \
+        ishmemx_wait_until_work_group<TYPE>(ivar, cmp, v, grp);                                    \
+    }                                                                                              \
+    template <typename Group>                                                                      \
+    __device__ inline int ishmemx_##TYPENAME##_test_work_group(TYPE *ivar, int cmp, TYPE v, const Group &grp)          \
+    {                                                                                              \
+        return ishmemx_test_work_group<TYPE>(ivar, cmp, v, grp);                                   \
+    }
+ISHMEMX_DEV_SYNC_TYPES(ISHMEMX_DEV_SYNC_TYPED)
 
 #endif /* ISHMEM_AMD_ISHMEMX_DEVICE_H */

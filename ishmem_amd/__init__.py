@@ -479,6 +479,136 @@ for _bits in (8, 16, 32, 64, 128):  # ishmem_put8 .. ishmem_get128 (elements of 
             setattr(_mod, _name, _f)
             RMA_NAMES.append(_name)
 del _tn, _kind, _name, _f, _put, _nbi, _bits
+
+# ---- put with signal, signal operations, wait_until / test (src/ishmem.h:28-36, :640-705, :1320-1354,
+#      :1551-1552) --------------------------------------------------------------------
+# The signal word (a symmetric uint64) is updated on the target only after the payload is in its
+# memory.  Like the C ABI, calls return 0 / nonzero unless they return a value; last_error() has the
+# reason, a timed-out wait included.
+ISHMEM_CMP_EQ, ISHMEM_CMP_NE, ISHMEM_CMP_GT, ISHMEM_CMP_GE, ISHMEM_CMP_LT, ISHMEM_CMP_LE = 1, 2, 3, 4, 5, 6
+ISHMEM_SIGNAL_SET, ISHMEM_SIGNAL_ADD = 0, 1
+# The 12 synchronisation typenames of ishmem_<TN>_wait_until / _test.
+SYNC_TYPENAMES = ["int", "long", "longlong", "uint", "ulong", "ulonglong", "int32", "int64", "uint32", "uint64",
+                  "size", "ptrdiff"]
+_U64 = (1 << 64) - 1
+
+
+def ishmem_putmem_signal(dest: int, source: int, nbytes: int, sig_addr: int, signal: int, sig_op: int, pe: int) -> int:
+    return _L.ishmemi_c_put_signal(dest, source, nbytes, sig_addr, signal & _U64, sig_op, pe)
+
+
+def ishmem_putmem_signal_nbi(dest: int, source: int, nbytes: int, sig_addr: int, signal: int, sig_op: int,
+                             pe: int) -> int:
+    return _L.ishmemi_c_put_signal_nbi(dest, source, nbytes, sig_addr, signal & _U64, sig_op, pe)
+
+
+def put_signal_on_stream(dest: int, source: int, nbytes: int, sig_addr: int, signal: int, sig_op: int, pe: int,
+                         stream: int, deps=(), done=None) -> int:
+    """ishmemx_putmem_signal_on_queue analogue (the _nbi form is the same call)."""
+    def call(d, s, n, p, st):
+        return _L.ishmemi_c_put_signal_on_stream(d, s, n, sig_addr, signal & _U64, sig_op, p, st)
+    return _rma_on_stream(call, dest, source, nbytes, pe, stream, deps, done)
+
+
+def ishmemx_signal_set(sig_addr: int, signal: int, pe: int) -> int:
+    return _L.ishmemi_c_signal_op(sig_addr, signal & _U64, ISHMEM_SIGNAL_SET, pe)
+
+
+def ishmemx_signal_add(sig_addr: int, signal: int, pe: int) -> int:
+    return _L.ishmemi_c_signal_op(sig_addr, signal & _U64, ISHMEM_SIGNAL_ADD, pe)
+
+
+def signal_fetch(sig_addr: int) -> tuple[int, int]:
+    """(status, value) of this PE's signal word."""
+    v = ctypes.c_uint64(0)
+    rc = _L.ishmemi_c_signal_fetch(sig_addr, ctypes.byref(v))
+    return rc, v.value
+
+
+def ishmem_signal_fetch(sig_addr: int) -> int:
+    return signal_fetch(sig_addr)[1]
+
+
+def wait_until(ivar: int, dtype: str, cmp: int, cmp_value: int) -> tuple[int, int]:
+    """(status, value read) — blocks until the `dtype` variable at `ivar` compares `cmp` against
+    `cmp_value`; status is nonzero after timeout_ms (value = the last one read) or a bad argument."""
+    v = ctypes.c_uint64(0)
+    rc = _L.ishmemi_c_wait_until(ivar, DTYPES.get(dtype, -1), cmp, cmp_value & _U64, ctypes.byref(v))
+    return rc, v.value
+
+
+def test(ivar: int, dtype: str, cmp: int, cmp_value: int) -> tuple[int, int]:
+    """(status, 1 / 0)."""
+    r = ctypes.c_int(0)
+    rc = _L.ishmemi_c_test(ivar, DTYPES.get(dtype, -1), cmp, cmp_value & _U64, ctypes.byref(r))
+    return rc, r.value
+
+
+test.__test__ = False  # a library call, not a pytest case
+
+
+def ishmem_signal_wait_until(sig_addr: int, cmp: int, cmp_value: int) -> int:
+    """The value that satisfied the comparison (after a timeout: the last value read)."""
+    return wait_until(sig_addr, "uint64", cmp, cmp_value)[1]
+
+
+def wait_until_on_stream(ivar: int, dtype: str, cmp: int, cmp_value: int, value_out: int, ret: int, stream: int,
+                         deps=(), done=None) -> int:
+    """ishmemx_<TN>_wait_until_on_queue analogue; *value_out / *ret (device-accessible, or 0)."""
+    def call(d, s, n, p, st):
+        return _L.ishmemi_c_wait_until_on_stream(ivar, DTYPES.get(dtype, -1), cmp, cmp_value & _U64, value_out or None,
+                                                 ret or None, st)
+    return _rma_on_stream(call, 0, 0, 0, 0, stream, deps, done)
+
+
+def signal_wait_until_on_stream(sig_addr: int, cmp: int, cmp_value: int, ret_value: int, stream: int, deps=(),
+                                done=None, ret: int = 0) -> int:
+    """ishmemx_signal_wait_until_on_queue analogue."""
+    return wait_until_on_stream(sig_addr, "uint64", cmp, cmp_value, ret_value, ret, stream, deps, done)
+
+
+def _make_put_signal(nbi: bool, size: int):
+    call = _L.ishmemi_c_put_signal_nbi if nbi else _L.ishmemi_c_put_signal
+
+    def fn(dest: int, source: int, nelems: int, sig_addr: int, signal: int, sig_op: int, pe: int) -> int:
+        return call(dest, source, nelems * size, sig_addr, signal & _U64, sig_op, pe)
+    return fn
+
+
+def _make_sync(dt: str, is_test: bool):
+    if is_test:
+        def fn(ivar: int, cmp: int, cmp_value: int) -> int:
+            return test(ivar, dt, cmp, cmp_value)[1]
+    else:
+        def fn(ivar: int, cmp: int, cmp_value: int) -> int:
+            return wait_until(ivar, dt, cmp, cmp_value)[0]
+    return fn
+
+
+SIGNAL_NAMES: list[str] = ["ishmem_putmem_signal", "ishmem_putmem_signal_nbi", "ishmem_signal_fetch",
+                           "ishmem_signal_wait_until", "ishmemx_signal_set", "ishmemx_signal_add"]
+for _tn in ARITH_TYPENAMES:
+    for _nbi in (False, True):
+        _name = f"ishmem_{_tn}_put_signal{'_nbi' if _nbi else ''}"
+        _f = _make_put_signal(_nbi, _SIZES[TYPENAMES[_tn]])
+        _f.__name__ = _name
+        setattr(_mod, _name, _f)
+        SIGNAL_NAMES.append(_name)
+for _bits in (8, 16, 32, 64, 128):
+    for _nbi in (False, True):
+        _name = f"ishmem_put{_bits}_signal{'_nbi' if _nbi else ''}"
+        _f = _make_put_signal(_nbi, _bits // 8)
+        _f.__name__ = _name
+        setattr(_mod, _name, _f)
+        SIGNAL_NAMES.append(_name)
+for _tn in SYNC_TYPENAMES:
+    for _is_test in (False, True):
+        _name = f"ishmem_{_tn}_{'test' if _is_test else 'wait_until'}"
+        _f = _make_sync(TYPENAMES[_tn], _is_test)
+        _f.__name__ = _name
+        setattr(_mod, _name, _f)
+        SIGNAL_NAMES.append(_name)
+del _tn, _name, _f, _nbi, _bits, _is_test
 API_NAMES: list[str] = []
 for _op, _tns in TYPENAMES_FOR_OP.items():
     for _tn in _tns:

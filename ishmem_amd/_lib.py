@@ -69,6 +69,14 @@ PROTOTYPES = [
     ("ishmemi_c_fence", _i, []),
     ("ishmemi_c_quiet_on_stream", _i, [_vp]),
     ("ishmemi_c_read_all_u32", _i, [_vp, _vp, _sz, _i, _vp]),
+    ("ishmemi_c_put_signal", _i, [_vp, _vp, _sz, _vp, _u64, _i, _i]),
+    ("ishmemi_c_put_signal_nbi", _i, [_vp, _vp, _sz, _vp, _u64, _i, _i]),
+    ("ishmemi_c_put_signal_on_stream", _i, [_vp, _vp, _sz, _vp, _u64, _i, _i, _vp]),
+    ("ishmemi_c_signal_op", _i, [_vp, _u64, _i, _i]),
+    ("ishmemi_c_signal_fetch", _i, [_vp, ctypes.POINTER(_u64)]),
+    ("ishmemi_c_wait_until", _i, [_vp, _i, _i, _u64, ctypes.POINTER(_u64)]),
+    ("ishmemi_c_test", _i, [_vp, _i, _i, _u64, ctypes.POINTER(_i)]),
+    ("ishmemi_c_wait_until_on_stream", _i, [_vp, _i, _i, _u64, _vp, _vp, _vp]),
     ("ishmemi_c_stream_wait_events", _i, [_vp, _vp, _sz]),
     ("ishmemi_c_stream_record_event", _i, [_vp, _vp]),
     ("ishmemi_c_collect", _i, [_i, _vp, _vp, _sz]),

@@ -321,4 +321,49 @@ hipError_t launch_rma_copy(const RmaArgs &a, bool put, int max_blocks, hipStream
 // Test hook: `grid` workgroups that each read all n words of p with plain loads into out[b * n ..].
 hipError_t launch_read_all_u32(uint32_t *out, const uint32_t *p, uint64_t n, int grid, hipStream_t s);
 
+// put with signal, signal operations and point-to-point waits (kernels_signal.hip).
+constexpr int kSignalSet = 0, kSignalAdd = 1;  // ISHMEM_SIGNAL_SET / ISHMEM_SIGNAL_ADD
+constexpr int kCmpEq = 1, kCmpLe = 6;          // ISHMEM_CMP_EQ .. ISHMEM_CMP_LE
+// `cmp` of two values of an integer type `width` bytes wide (4 or 8), compared in that type: the low
+// `width` bytes of each, sign-extended when `is_signed`.
+__host__ __device__ inline bool signal_compare(uint64_t v, int cmp, uint64_t c, int width, int is_signed)
+{
+    if (width == 4) {
+        v = is_signed ? (uint64_t) (int64_t) (int32_t) (uint32_t) v : (uint64_t) (uint32_t) v;
+        c = is_signed ? (uint64_t) (int64_t) (int32_t) (uint32_t) c : (uint64_t) (uint32_t) c;
+    }
+    const bool lt = is_signed ? (int64_t) v < (int64_t) c : v < c;
+    switch (cmp) {
+        case 1: return v == c;
+        case 2: return v != c;
+        case 3: return !lt && v != c;
+        case 4: return !lt;
+        case 5: return lt;
+        case 6: return lt || v == c;
+        default: return false;
+    }
+}
+// The fused put + signal: ONE workgroup copies the payload (rma_copy_kernel<true>'s layout and
+// cache policy), every wave drains its stores, then one lane updates the signal word `sig` (a peer's
+// heap as mapped here) with a system-scope atomic store (kSignalSet) or add (kSignalAdd).
+hipError_t launch_put_signal(const RmaArgs &a, uint64_t *sig, uint64_t value, int sig_op, hipStream_t s);
+// One lane, one system-scope atomic on `sig`.
+hipError_t launch_signal_op(uint64_t *sig, uint64_t value, int sig_op, hipStream_t s);
+// One wave; lane 0 polls the word at `ivar` (this PE's heap; `width` 4 or 8) with relaxed system-scope
+// loads until `cmp` against `cmp_value` holds, `budget` polls were made (0 = no budget) or
+// `timeout_ticks` passed.  Then *value_out = the last value read (zero- or sign-extended to 64 bits)
+// and *status_out = kWaitMatched / kWaitTimedOut / kWaitNoMatch (either may be null; device-accessible
+// addresses); a timeout also ORs kWaitErrBit into *err when err is not null.
+constexpr int kWaitMatched = 0, kWaitTimedOut = 1, kWaitNoMatch = 2;
+constexpr uint32_t kWaitErrBit = 1u << 8;
+struct WaitArgs {
+    const void *ivar;
+    int width, is_signed, cmp;
+    uint64_t cmp_value, budget, timeout_ticks;
+    uint64_t *value_out;
+    int *status_out;
+    uint32_t *err;
+};
+hipError_t launch_signal_wait(const WaitArgs &a, hipStream_t s);
+
 }  // namespace ishmemi

@@ -36,8 +36,9 @@
 //     completes whatever part of the grid is resident.  All remote payload accesses of the
 //     COLLECTIVES outside the granule rings are LOADS (pull), so no collective leaves a PE's L2
 //     with stale copies of bytes a peer wrote; the rings are uncached fine-grained memory written
-//     and polled with system-scope atomics.  put (kernels_rma.hip) is the one path that stores
-//     payload into a peer's heap; its visibility contract is DESIGN.md §3b.
+//     and polled with system-scope atomics.  put (kernels_rma.hip) and put with signal
+//     (kernels_signal.hip) are the paths that store payload into a peer's heap; their visibility
+//     and ordering contracts are DESIGN.md §3b and §3c.
 #pragma once
 #include <algorithm>
 #include <map>

@@ -253,7 +253,7 @@ void warn_unknown_env()
         "PE", "NPES", "DEVICE", "BOOTSTRAP_KEY", "TIMEOUT_MS", "MAX_BLOCKS", "WAIT_SLOTS", "LL_MAX_BYTES",
         "ONESHOT_P2_MAX_BYTES", "PHASED_MIN_BYTES", "PHASED_PEER_NT", "STAGING_SIZE", "STAGING_SLOTS",
         "STAGED_COPY_KERNEL", "STREAM_ORDER", "FLAGS_KIND", "EP_UNCACHED", "BARRIER_KIND", "XGMI_LL_MAX_BYTES",
-        "XGMI_FOLD_MAX_BYTES", "TEST_FLAGS_UNAVAILABLE", "TEST_PCI_BUS",
+        "XGMI_FOLD_MAX_BYTES", "PUT_SIGNAL_FUSED_MAX_BYTES", "TEST_FLAGS_UNAVAILABLE", "TEST_PCI_BUS",
         // the Python package, build and bench harness
         "AMD_LIB", "OFFLOAD_ARCH", "BENCH_SAME_DEVICE", "BENCH_EMULATE_SHARE1", "BENCH_SETUP_WATCHDOG_S"};
     for (char **e = ::environ; e && *e; ++e) {
@@ -339,6 +339,16 @@ struct PeRecord {
     hipIpcMemHandle_t flags_handle;
 };
 
+// Measured crossover of the one-workgroup kernel against put grid + signal kernel, rounded down to a
+// power of two (tools/signal_sweep.py, profiles/signal/sweep_p2.csv: 4.4 against 5.9 us at 32 KiB, 6.7
+// against 5.9 us at 64 KiB).
+constexpr long long kPutSignalFusedDefault = 32 << 10;
+constexpr int kWaitSlots = 16;
+// A blocking host wait polls in kernels of at most this long (100 MHz ticks) and launches the next
+// one from the host: work of another host thread that HIP placed on the same hardware queue as the
+// waiter's stream runs between two of them instead of behind a kernel that waits for that very work.
+constexpr uint64_t kWaitSliceTicks = 100000;  // 1 ms
+
 struct State {
     std::mutex mu;
     bool initialized = false;
@@ -384,6 +394,17 @@ struct State {
     hipStream_t rma_stream = nullptr;
     hipEvent_t rma_ev = nullptr;
     bool rma_pending = false;
+    // put_signal: payloads up to this many bytes take the fused one-workgroup kernel, larger ones the
+    // put grid followed by the one-lane signal kernel (ISHMEM_PUT_SIGNAL_FUSED_MAX_BYTES, set_param
+    // "put_signal_fused_max_bytes"; the origin alone chooses, nothing pairs across PEs).
+    long long put_signal_fused_max = kPutSignalFusedDefault;
+    // Blocking host waits / test / signal_fetch: kWaitSlots slots, each a non-blocking stream of its
+    // own (created at first use; never the null stream, never rma_stream) and a line of pinned host
+    // memory the wait kernel writes {value, status} into.  A slot is held by one host thread for one
+    // call; s.mu is taken to validate, launch and release, never while waiting.
+    hipStream_t wait_stream[kWaitSlots] = {};
+    bool wait_busy[kWaitSlots] = {};
+    char *wait_host = nullptr, *wait_dev = nullptr;  // kWaitSlots lines of 64 B
     // Stream of the previous collective: a collective enqueued on another stream first waits
     // for it, so epochs, flag rows and the staging region are used in call order.
     hipStream_t last_stream = nullptr;
@@ -1642,6 +1663,240 @@ int rma_impl(bool put, void *dest, const void *source, size_t nbytes, int pe, Rm
     return host_wait(s, st);
 }
 
+// ---------------- put with signal, signal operations, wait_until / test ----------
+// ishmem_put_signal / ishmemx_signal_set / add / ishmem_signal_fetch / ishmem_signal_wait_until /
+// ishmem_<TN>_wait_until / _test (src/signaling.cpp, src/synchronization.cpp).  The payload goes
+// where put's goes; the signal word is updated only after every payload byte is in the target's
+// memory: inside one workgroup (payloads up to put_signal_fused_max_bytes: kernels_signal.hip), or by
+// a one-lane kernel behind the put's grid on the same stream.
+
+// A symmetric 8-byte signal word / a 4- or 8-byte synchronisation variable of this PE.
+const char *sync_word_error(const State &s, const void *p, size_t width)
+{
+    if (!p) return " is null";
+    if ((uintptr_t) p % width) return width == 8 ? " is not 8-byte aligned" : " is not 4-byte aligned";
+    if (!in_heap(s, p) || width > (size_t) (s.heap + s.heap_size - (const char *) p)) return " is not inside the symmetric heap";
+    return nullptr;
+}
+
+hipStream_t rma_kind_stream(State &s, RmaKind kind, hipStream_t user, int &rc)
+{
+    rc = 0;
+    if (kind == kRmaNbi) {
+        if (!s.rma_stream && hipStreamCreateWithFlags(&s.rma_stream, hipStreamNonBlocking) != hipSuccess) {
+            rc = fail("_nbi: cannot create the library's stream");
+            return nullptr;
+        }
+        return s.rma_stream;
+    }
+    if (kind == kRmaOnStream) {
+        rc = order_stream(s, user);
+        return user;
+    }
+    return nullptr;
+}
+
+int rma_kind_finish(State &s, RmaKind kind, hipStream_t st)
+{
+    if (kind == kRmaNbi) {
+        s.rma_pending = true;
+        return 0;
+    }
+    if (kind == kRmaOnStream) return mark_stream(s, st);
+    return host_wait(s, st);
+}
+
+int put_signal_impl(void *dest, const void *source, size_t nbytes, uint64_t *sig, uint64_t value, int sig_op, int pe,
+                    RmaKind kind, hipStream_t user)
+{
+    const std::string what = std::string("put_signal") + (kind == kRmaNbi ? "_nbi" : kind == kRmaOnStream ? "_on_stream" : "");
+    State &s = S();
+    std::lock_guard<std::mutex> lk(s.mu);
+    if (!s.initialized) return fail(what + ": not initialized");
+    if (pe < 0 || pe >= s.npes)
+        return fail(what + ": pe " + std::to_string(pe) + " outside [0, " + std::to_string(s.npes) + ")");
+    if (sig_op != kSignalSet && sig_op != kSignalAdd)
+        return fail(what + ": sig_op " + std::to_string(sig_op) + " is neither ISHMEM_SIGNAL_SET nor ISHMEM_SIGNAL_ADD");
+    if (const char *e = sync_word_error(s, sig, 8)) return fail(what + ": sig_addr" + e);
+    uint64_t *rsig = (uint64_t *) translate(s, sig, pe);
+    if (!rsig) return fail(what + ": heap of PE " + std::to_string(pe) + " not mapped");
+    char *remote = nullptr, *local = nullptr;
+    if (nbytes) {
+        if (!dest || !source) return fail(what + ": null pointer with nbytes > 0");
+        if (!in_heap(s, dest) || nbytes > (size_t) (s.heap + s.heap_size - (const char *) dest))
+            return fail(what + ": dest is not inside the symmetric heap for its whole length");
+        remote = translate(s, dest, pe);
+        local = device_view(s, source);
+        if (!local && kind != kRmaBlocking)
+            return fail(what + ": source is not device-accessible (heap, device or pinned host memory; pageable host "
+                        "memory is accepted by the blocking host forms only)");
+    }
+    int rc = 0;
+    hipStream_t st = rma_kind_stream(s, kind, user, rc);
+    if (rc) return 1;
+    if (nbytes == 0) {
+        HIP_TRY(launch_signal_op(rsig, value, sig_op, st));
+    } else if (!local) {
+        // Pageable source: the copy has completed when hipMemcpy returns, then the signal.
+        HIP_TRY(hipMemcpy(remote, source, nbytes, hipMemcpyHostToDevice));
+        HIP_TRY(launch_signal_op(rsig, value, sig_op, st));
+    } else {
+        RmaArgs a{};
+        a.dst = remote;
+        a.src = local;
+        a.head = std::min<uint64_t>(nbytes, (16 - ((uintptr_t) a.dst & 15)) & 15);
+        a.nitems = (nbytes - a.head) / 16;
+        a.tail = nbytes - a.head - a.nitems * 16;
+        if ((long long) std::min<size_t>(nbytes, (size_t) std::numeric_limits<long long>::max()) <= s.put_signal_fused_max) {
+            HIP_TRY(launch_put_signal(a, rsig, value, sig_op, st));
+        } else {
+            HIP_TRY(launch_rma_copy(a, true, s.max_blocks, st));
+            HIP_TRY(launch_signal_op(rsig, value, sig_op, st));
+        }
+    }
+    return rma_kind_finish(s, kind, st);
+}
+
+int signal_op_impl(uint64_t *sig, uint64_t value, int sig_op, int pe)
+{
+    State &s = S();
+    std::lock_guard<std::mutex> lk(s.mu);
+    if (!s.initialized) return fail("signal_op: not initialized");
+    if (pe < 0 || pe >= s.npes)
+        return fail("signal_op: pe " + std::to_string(pe) + " outside [0, " + std::to_string(s.npes) + ")");
+    if (sig_op != kSignalSet && sig_op != kSignalAdd)
+        return fail("signal_op: sig_op " + std::to_string(sig_op) + " is neither ISHMEM_SIGNAL_SET nor ISHMEM_SIGNAL_ADD");
+    if (const char *e = sync_word_error(s, sig, 8)) return fail(std::string("signal_op: sig_addr") + e);
+    uint64_t *rsig = (uint64_t *) translate(s, sig, pe);
+    if (!rsig) return fail("signal_op: heap of PE " + std::to_string(pe) + " not mapped");
+    HIP_TRY(launch_signal_op(rsig, value, sig_op, 0));
+    return host_wait(s, 0);
+}
+
+// The synchronisation dtypes: the 32- and 64-bit integers.
+bool sync_dtype(int dt, int &width, int &is_signed)
+{
+    switch (dt) {
+        case ISHMEMI_DT_INT32: width = 4; is_signed = 1; return true;
+        case ISHMEMI_DT_UINT32: width = 4; is_signed = 0; return true;
+        case ISHMEMI_DT_INT64: width = 8; is_signed = 1; return true;
+        case ISHMEMI_DT_UINT64: width = 8; is_signed = 0; return true;
+        default: return false;
+    }
+}
+
+int wait_args(const State &s, const char *what, void *ivar, int dt, int cmp, uint64_t cmp_bits, WaitArgs &a)
+{
+    if (!s.initialized) return fail(std::string(what) + ": not initialized");
+    a = WaitArgs{};
+    if (!sync_dtype(dt, a.width, a.is_signed))
+        return fail(std::string(what) + ": dtype " + std::to_string(dt) + " is not a 32- or 64-bit integer type");
+    if (cmp < kCmpEq || cmp > kCmpLe)
+        return fail(std::string(what) + ": cmp " + std::to_string(cmp) + " is not one of ISHMEM_CMP_EQ .. ISHMEM_CMP_LE");
+    if (const char *e = sync_word_error(s, ivar, (size_t) a.width)) return fail(std::string(what) + ": ivar" + e);
+    a.ivar = ivar;
+    a.cmp = cmp;
+    a.cmp_value = cmp_bits;
+    return 0;
+}
+
+// Blocking host wait (budget 0), test or fetch (budget 1).  *status: kWaitMatched / kWaitNoMatch;
+// a timeout returns nonzero, counts as an error and still leaves the last value read in *value.
+int host_wait_until(const char *what, void *ivar, int dt, int cmp, uint64_t cmp_bits, uint64_t budget, uint64_t *value,
+                    int *status)
+{
+    State &s = S();
+    WaitArgs a{};
+    int slot = -1;
+    hipStream_t st = nullptr;
+    volatile uint64_t *hv = nullptr;
+    volatile int *hs = nullptr;
+    uint64_t total_ticks = 0;
+    {
+        std::lock_guard<std::mutex> lk(s.mu);
+        if (wait_args(s, what, ivar, dt, cmp, cmp_bits, a)) return 1;
+        if (!s.wait_host) {
+            HIP_TRY(hipHostMalloc((void **) &s.wait_host, (size_t) kWaitSlots * 64, hipHostMallocMapped | hipHostMallocCoherent));
+            HIP_TRY(hipHostGetDevicePointer((void **) &s.wait_dev, s.wait_host, 0));
+        }
+        for (int k = 0; k < kWaitSlots && slot < 0; ++k)
+            if (!s.wait_busy[k]) slot = k;
+        if (slot < 0) return fail(std::string(what) + ": more than " + std::to_string(kWaitSlots) + " host threads are waiting at once");
+        if (!s.wait_stream[slot]) HIP_TRY(hipStreamCreateWithFlags(&s.wait_stream[slot], hipStreamNonBlocking));
+        s.wait_busy[slot] = true;
+        st = s.wait_stream[slot];
+        hv = (volatile uint64_t *) (s.wait_host + (size_t) slot * 64);
+        hs = (volatile int *) (s.wait_host + (size_t) slot * 64 + 8);
+        a.value_out = (uint64_t *) (s.wait_dev + (size_t) slot * 64);
+        a.status_out = (int *) (s.wait_dev + (size_t) slot * 64 + 8);
+        a.budget = budget;
+        total_ticks = (uint64_t) s.timeout_ms * 100000ull;
+    }
+    int result = kWaitNoMatch;
+    std::string hiperr;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+        // The lock is held to launch only: another host thread may be the one that issues the put
+        // this PE's peer is waiting for before it signals back.
+        const auto waited = std::chrono::steady_clock::now() - t0;
+        const uint64_t used = (uint64_t) std::chrono::duration_cast<std::chrono::microseconds>(waited).count() * 100ull;
+        a.timeout_ticks = std::min<uint64_t>(kWaitSliceTicks, total_ticks > used ? total_ticks - used : 1);
+        __atomic_store_n((int *) hs, -1, __ATOMIC_RELEASE);
+        hipError_t e;
+        {
+            std::lock_guard<std::mutex> lk(s.mu);
+            e = launch_signal_wait(a, st);
+        }
+        if (e == hipSuccess) {
+            int spins = 0;
+            const auto l0 = std::chrono::steady_clock::now();
+            while (__atomic_load_n((int *) hs, __ATOMIC_ACQUIRE) == -1) {
+                __builtin_ia32_pause();
+                if (++spins == 4096) {
+                    spins = 0;
+                    if (std::chrono::steady_clock::now() - l0 > std::chrono::milliseconds(50)) break;
+                }
+            }
+            if (__atomic_load_n((int *) hs, __ATOMIC_ACQUIRE) == -1) e = hipStreamSynchronize(st);
+        }
+        if (e != hipSuccess) {
+            hiperr = hipGetErrorString(e);
+            break;
+        }
+        result = __atomic_load_n((int *) hs, __ATOMIC_ACQUIRE);
+        if (result == kWaitMatched || budget) break;
+        if (used + a.timeout_ticks >= total_ticks) break;  // result == kWaitTimedOut: the whole bound has passed
+    }
+    if (value) *value = *hv;
+    std::lock_guard<std::mutex> lk(s.mu);
+    s.wait_busy[slot] = false;
+    if (!hiperr.empty()) return fail(std::string(what) + ": " + hiperr);
+    if (status) *status = result == kWaitMatched ? kWaitMatched : kWaitNoMatch;
+    if (result == kWaitTimedOut && !budget) {
+        s.error_count++;
+        return fail(std::string(what) + ": timed out after timeout_ms (" + std::to_string(s.timeout_ms) +
+                    " ms): the condition did not become true");
+    }
+    return 0;
+}
+
+int wait_until_on_stream_impl(void *ivar, int dt, int cmp, uint64_t cmp_bits, uint64_t *value, int *ret, hipStream_t st)
+{
+    State &s = S();
+    std::lock_guard<std::mutex> lk(s.mu);
+    WaitArgs a{};
+    if (wait_args(s, "wait_until_on_stream", ivar, dt, cmp, cmp_bits, a)) return 1;
+    // No order_stream / mark_stream: with stream_order on, later calls on other streams must not
+    // queue behind somebody's wait.  Poll target and compare value are frozen kernel arguments, so
+    // the call can be captured into a graph.
+    a.timeout_ticks = (uint64_t) s.timeout_ms * 100000ull;
+    a.value_out = value;
+    a.status_out = ret;
+    a.err = s.err_dev + kMaxTeams;
+    HIP_TRY(launch_signal_wait(a, st));
+    return 0;
+}
+
 int scan_impl(int team, int dt, int inclusive, void *dst, const void *src, size_t n, int *ret,
               hipStream_t st, bool blocking)
 {
@@ -2032,6 +2287,7 @@ int init_impl(int pe, int npes, int device, const std::string &key)
     s.xgmi_ll_max = std::max<long long>(-1, env_bytes("ISHMEM_XGMI_LL_MAX_BYTES", -1));
     s.xgmi_fold_max = std::max<long long>(-1, env_bytes("ISHMEM_XGMI_FOLD_MAX_BYTES", -1));
     s.xgmi_link_bps = 76.8e9;
+    s.put_signal_fused_max = std::max<long long>(0, env_bytes("ISHMEM_PUT_SIGNAL_FUSED_MAX_BYTES", kPutSignalFusedDefault));
     // Round 5's stream-memory-op barrier was removed in round 6 (team_barrier): "kernel" is still
     // accepted, "stream" is refused rather than silently ignored.
     if (const char *bk = getenv("ISHMEM_BARRIER_KIND"); bk && *bk && strcasecmp(bk, "kernel") != 0 && g_env_error.empty())
@@ -2591,6 +2847,13 @@ int ishmemi_c_finalize(void)
     s.rma_stream = nullptr;
     s.rma_ev = nullptr;
     s.rma_pending = false;
+    for (int k = 0; k < kWaitSlots; ++k) {
+        if (s.wait_stream[k]) (void) hipStreamDestroy(s.wait_stream[k]);
+        s.wait_stream[k] = nullptr;
+        s.wait_busy[k] = false;
+    }
+    if (s.wait_host) (void) hipHostFree(s.wait_host);
+    s.wait_host = s.wait_dev = nullptr;
     if (s.phase_ev[0])
         for (hipEvent_t &e : s.phase_ev) {
             (void) hipEventDestroy(e);
@@ -3143,6 +3406,53 @@ int ishmemi_c_quiet_on_stream(void *stream)
     return 0;
 }
 
+int ishmemi_c_put_signal(void *dest, const void *source, size_t nbytes, uint64_t *sig, uint64_t value, int sig_op, int pe)
+{
+    return put_signal_impl(dest, source, nbytes, sig, value, sig_op, pe, kRmaBlocking, 0);
+}
+
+int ishmemi_c_put_signal_nbi(void *dest, const void *source, size_t nbytes, uint64_t *sig, uint64_t value, int sig_op,
+                             int pe)
+{
+    return put_signal_impl(dest, source, nbytes, sig, value, sig_op, pe, kRmaNbi, 0);
+}
+
+int ishmemi_c_put_signal_on_stream(void *dest, const void *source, size_t nbytes, uint64_t *sig, uint64_t value,
+                                   int sig_op, int pe, void *stream)
+{
+    return put_signal_impl(dest, source, nbytes, sig, value, sig_op, pe, kRmaOnStream, (hipStream_t) stream);
+}
+
+int ishmemi_c_signal_op(uint64_t *sig, uint64_t value, int sig_op, int pe) { return signal_op_impl(sig, value, sig_op, pe); }
+
+int ishmemi_c_signal_fetch(uint64_t *sig, uint64_t *value)
+{
+    // One poll; whether it compared equal to 0 is not looked at, only the value read.
+    uint64_t v = 0;
+    const int rc = host_wait_until("signal_fetch", sig, ISHMEMI_DT_UINT64, kCmpEq, 0, 1, &v, nullptr);
+    if (rc == 0 && value) *value = v;
+    return rc;
+}
+
+int ishmemi_c_wait_until(void *ivar, int dtype, int cmp, uint64_t cmp_value_bits, uint64_t *value)
+{
+    return host_wait_until("wait_until", ivar, dtype, cmp, cmp_value_bits, 0, value, nullptr);
+}
+
+int ishmemi_c_test(void *ivar, int dtype, int cmp, uint64_t cmp_value_bits, int *result)
+{
+    int status = kWaitNoMatch;
+    const int rc = host_wait_until("test", ivar, dtype, cmp, cmp_value_bits, 1, nullptr, &status);
+    if (result) *result = (rc == 0 && status == kWaitMatched) ? 1 : 0;
+    return rc;
+}
+
+int ishmemi_c_wait_until_on_stream(void *ivar, int dtype, int cmp, uint64_t cmp_value_bits, uint64_t *value, int *ret,
+                                   void *stream)
+{
+    return wait_until_on_stream_impl(ivar, dtype, cmp, cmp_value_bits, value, ret, (hipStream_t) stream);
+}
+
 int ishmemi_c_resync(void)
 {
     // After a device-side timeout the members of a team disagree on its epoch (a PE that timed
@@ -3552,6 +3862,7 @@ int ishmemi_c_set_param(const char *name, long long value)
     else if (n == "oneshot_p2_max_bytes") s.oneshot_p2 = std::max<long long>(0, value);
     else if (n == "phased_min_bytes") s.phased_min = value < 0 ? kPhasedOff : value;
     else if (n == "ll_max_bytes") s.ll_max_bytes = std::min<long long>((long long) kLLMaxBytes, std::max<long long>(0, value));
+    else if (n == "put_signal_fused_max_bytes") s.put_signal_fused_max = std::max<long long>(0, value);  // per PE
     else if (n == "debug") s.debug = (int) value;
     else if (n == "phased_peer_nt") s.phased_peer_nt = value != 0;
     else if (n == "xgmi_ll_max_bytes") s.xgmi_ll_max = std::max<long long>(-1, value);      // alike on every PE
@@ -3591,6 +3902,7 @@ long long ishmemi_c_get_param(const char *name)
     if (n == "oneshot_p2_max_bytes") return s.oneshot_p2;
     if (n == "phased_min_bytes") return s.phased_min == kPhasedOff ? -1 : s.phased_min;
     if (n == "ll_max_bytes") return s.ll_max_bytes;
+    if (n == "put_signal_fused_max_bytes") return s.put_signal_fused_max;
     if (n == "ll_capacity_bytes") return (long long) ll_capacity(s.npes);  // TEAM_WORLD's ring capacity
     // TEAM_WORLD's thresholds (path_limits: by its topology, co-located or across GPUs).
     if (n == "ll_limit_bytes") return team_limits(s, s.teams[0]).ll;
