@@ -23,6 +23,7 @@
 
 #include <type_traits>
 
+#include "ishmem_amo.h"
 #include "ishmem_capi.h"
 
 /* ---- version, threading (src/ishmem.h:17-26) ---------------------------------------------- */
@@ -577,6 +578,44 @@ inline int ishmem_test(T *ivar, int cmp, T cmp_value)
     inline void ishmem_##TYPENAME##_wait_until(TYPE *ivar, int cmp, TYPE v) { ishmem_wait_until<TYPE>(ivar, cmp, v); } \
     inline int ishmem_##TYPENAME##_test(TYPE *ivar, int cmp, TYPE v) { return ishmem_test<TYPE>(ivar, cmp, v); }
 ISHMEMI_CXX_SYNC_TYPES(ISHMEMI_CXX_SYNC_TYPED)
+
+/* ---- atomic memory operations (src/ishmem.h:331-640, src/amo.cpp) ----------------------------------
+ * ishmem_atomic_<op>[_nbi]<T> and ishmem_<TYPENAME>_atomic_<op>[_nbi], generated by ishmem_amo.h (type
+ * lists and signatures there).  Host forms; the device-callable forms of the same names are in
+ * ishmemx_device.h.  void / value returning, as in the reference: a failure leaves its reason in
+ * ishmemi_c_last_error() and a fetching name then returns T().  An _nbi form's *fetch (symmetric heap,
+ * device or pinned host memory) is defined after ishmem_quiet.  float and double travel as bits.
+ * Atomicity and ordering against puts: DESIGN.md §3d. */
+namespace ishmemi_cxx {
+template <typename T>
+inline uint64_t amo_bits(T v)
+{
+    ishmemi_amo::bits_t<T> b;
+    __builtin_memcpy(&b, &v, sizeof(T));
+    return (uint64_t) b;
+}
+template <typename T>
+inline T amo_f(int op, T *dest, T val, T cond, int pe)
+{
+    uint64_t f = 0;
+    if (ishmemi_c_amo(op, ishmemi_amo::dtype<T>(), (void *) dest, amo_bits(val), amo_bits(cond), pe, &f)) return T();
+    const ishmemi_amo::bits_t<T> b = (ishmemi_amo::bits_t<T>) f;
+    T r;
+    __builtin_memcpy(&r, &b, sizeof(T));
+    return r;
+}
+template <typename T>
+inline void amo_v(int op, T *dest, T val, int pe)
+{
+    (void) ishmemi_c_amo(op, ishmemi_amo::dtype<T>(), (void *) dest, amo_bits(val), 0, pe, nullptr);
+}
+template <typename T>
+inline void amo_n(int op, T *fetch, T *dest, T val, T cond, int pe)
+{
+    (void) ishmemi_c_amo_nbi(op, ishmemi_amo::dtype<T>(), (void *) fetch, (void *) dest, amo_bits(val), amo_bits(cond), pe);
+}
+}  // namespace ishmemi_cxx
+ISHMEMI_AMO_DEFINE_ALL(inline, ishmemi_cxx)
 
 /* Compiled as HIP: the device-callable half of this API (the reference's SYCL_EXTERNAL functions:
  * ishmem_my_pe / ishmem_<TN>_<op>_reduce / ... from inside a kernel, ishmemx_*_work_group). */

@@ -324,6 +324,38 @@ int ishmemi_c_test(void *ivar, int dtype, int cmp, uint64_t cmp_value_bits, int 
 int ishmemi_c_wait_until_on_stream(void *ivar, int dtype, int cmp, uint64_t cmp_value_bits, uint64_t *value, int *ret,
                                    void *stream);
 
+/* ---- atomic memory operations — ishmem_<TN>_atomic_<op>[_nbi] (src/ishmem.h:331-640, src/amo.cpp,
+ *      src/amo_impl.h) ---------------------------------------------------------------------------------
+ * One relaxed, system-scope atomic operation `op` (ISHMEMI_C_AMO_*) on the word at `dest` on `pe`
+ * (this PE's symmetric address, naturally aligned, inside the heap; pe == my_pe is legal).  `dtype`:
+ * ISHMEMI_DT_INT32 / UINT32 / INT64 / UINT64 for every op, ISHMEMI_DT_FLOAT / DOUBLE for FETCH, SET and
+ * SWAP only (the narrower per-typename lists of the reference are enforced by include/ishmem.h).
+ * Operands and results are the value's bits, zero-extended; no result depends on signedness.
+ *   amo      blocking; *fetched_bits (may be null) = the word's old value for a fetching op, else 0;
+ *   amo_nbi  the eight fetching ops only, enqueued where put_nbi goes; the old value is stored to
+ *            `fetch` (non-null, aligned; heap, device or pinned host memory — pageable memory is
+ *            refused) and is defined after ishmemi_c_quiet / quiet_on_stream / barrier_all.
+ * INC / FETCH_INC ignore value_bits; cond_bits is COMPARE_SWAP's.  Argument errors return nonzero
+ * before anything is launched and do not move ishmemi_c_error_count.  Atomicity and ordering against
+ * puts: DESIGN.md §3d. */
+#define ISHMEMI_C_AMO_FETCH 0
+#define ISHMEMI_C_AMO_SET 1
+#define ISHMEMI_C_AMO_COMPARE_SWAP 2
+#define ISHMEMI_C_AMO_SWAP 3
+#define ISHMEMI_C_AMO_FETCH_INC 4
+#define ISHMEMI_C_AMO_INC 5
+#define ISHMEMI_C_AMO_FETCH_ADD 6
+#define ISHMEMI_C_AMO_ADD 7
+#define ISHMEMI_C_AMO_FETCH_AND 8
+#define ISHMEMI_C_AMO_AND 9
+#define ISHMEMI_C_AMO_FETCH_OR 10
+#define ISHMEMI_C_AMO_OR 11
+#define ISHMEMI_C_AMO_FETCH_XOR 12
+#define ISHMEMI_C_AMO_XOR 13
+#define ISHMEMI_C_AMO_COUNT 14
+int ishmemi_c_amo(int op, int dtype, void *dest, uint64_t value_bits, uint64_t cond_bits, int pe, uint64_t *fetched_bits);
+int ishmemi_c_amo_nbi(int op, int dtype, void *fetch, void *dest, uint64_t value_bits, uint64_t cond_bits, int pe);
+
 /* ---- device-initiated collectives ----------------------------------------------------------
  * The reference's device-callable reductions (ishmemx_<TN>_<op>_reduce_work_group,
  * src/collectives/reduce_impl.h:386-418, :505-518, src/ishmemx.h:1648-1699) read the library

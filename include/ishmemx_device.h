@@ -12,6 +12,7 @@
  *       ishmemx_*_{put,get}[_nbi]_work_group, ishmem_quiet / fence, ishmemx_quiet / fence_work_group;
  *   ishmem_<TYPENAME>_put_signal[_nbi], ishmemx_*_put_signal[_nbi]_work_group, ishmemx_signal_set / add,
  *       ishmem_signal_fetch / signal_wait_until, ishmem_<TYPENAME>_wait_until / _test and *_work_group;
+ *   ishmem_<TYPENAME>_atomic_<op>[_nbi] and ishmem_atomic_<op>[_nbi]<T> from any work-item (ishmem_amo.h);
  *   ishmem_my_pe / n_pes / team_my_pe / team_n_pes / team_translate_pe / ptr / info_get_*,
  *   ishmem_barrier_all / sync_all / team_sync and their *_work_group forms, ishmemx_print.
  * `grp` is a HIP cooperative group — cooperative_groups::thread_block (the reference's
@@ -48,6 +49,7 @@
 
 #include <type_traits>
 
+#include "ishmem_amo.h"
 #include "ishmem_capi.h"
 
 namespace ishmemx_dev {
@@ -1397,5 +1399,70 @@ __device__ inline int ishmemx_test_work_group(T *ivar, int cmp, T cmp_value, con
         return ishmemx_test_work_group<TYPE>(ivar, cmp, v, grp);                                   \
     }
 ISHMEMX_DEV_SYNC_TYPES(ISHMEMX_DEV_SYNC_TYPED)
+
+/* ---- atomic memory operations from a kernel (src/ishmem.h:331-640) -----------------
+ * ishmem_atomic_<op>[_nbi]<T> and ishmem_<TYPENAME>_atomic_<op>[_nbi] (ishmem_amo.h), callable by one
+ * work-item; every lane of a wave may call, with the same or with different dest / pe.  One relaxed
+ * system-scope builtin on the word's bits at the peer-mapped address: no compare-and-swap loop, the
+ * vector path.  A fetching form returns the old value; an _nbi form stores it to *fetch, valid after
+ * the calling work-item's ishmem_quiet(); a non-fetching form is a no-return atomic, complete after
+ * ishmem_quiet() / ishmem_fence() (their s_waitcnt vmcnt(0) counts it).  AMOs order nothing else by
+ * themselves.  A pe outside [0, npes) returns at once, a fetching form T(). */
+namespace ishmemx_dev {
+template <typename U>
+__device__ __forceinline__ U amo_rmw(int op, U *p, U v, U cond)
+{
+    constexpr int kOrder = __ATOMIC_RELAXED, kScope = __HIP_MEMORY_SCOPE_SYSTEM;
+    switch (op) {
+        case ISHMEMI_C_AMO_FETCH: return __hip_atomic_load(p, kOrder, kScope);
+        case ISHMEMI_C_AMO_SWAP: return __hip_atomic_exchange(p, v, kOrder, kScope);
+        case ISHMEMI_C_AMO_COMPARE_SWAP:
+            (void) __hip_atomic_compare_exchange_strong(p, &cond, v, kOrder, kOrder, kScope);
+            return cond;  // the word's value before the operation, whether it matched or not
+        case ISHMEMI_C_AMO_FETCH_INC: return __hip_atomic_fetch_add(p, (U) 1, kOrder, kScope);
+        case ISHMEMI_C_AMO_FETCH_ADD: return __hip_atomic_fetch_add(p, v, kOrder, kScope);
+        case ISHMEMI_C_AMO_FETCH_AND: return __hip_atomic_fetch_and(p, v, kOrder, kScope);
+        case ISHMEMI_C_AMO_FETCH_OR: return __hip_atomic_fetch_or(p, v, kOrder, kScope);
+        default: return __hip_atomic_fetch_xor(p, v, kOrder, kScope);
+    }
+}
+template <typename T>
+__device__ __forceinline__ T amo_f(int op, T *dest, T val, T cond, int pe)
+{
+    using U = ishmemi_amo::bits_t<T>;
+    const ishmemi_c_device_ctx_t *c = ctx();
+    if (!c || pe < 0 || pe >= c->npes) return T();
+    const U old = amo_rmw<U>(op, (U *) peer_addr(c, dest, pe), __builtin_bit_cast(U, val), __builtin_bit_cast(U, cond));
+    return __builtin_bit_cast(T, old);
+}
+template <typename T>
+__device__ __forceinline__ void amo_v(int op, T *dest, T val, int pe)
+{
+    using U = ishmemi_amo::bits_t<T>;
+    constexpr int kOrder = __ATOMIC_RELAXED, kScope = __HIP_MEMORY_SCOPE_SYSTEM;
+    const ishmemi_c_device_ctx_t *c = ctx();
+    if (!c || pe < 0 || pe >= c->npes) return;
+    U *p = (U *) peer_addr(c, dest, pe);
+    const U v = __builtin_bit_cast(U, val);
+    switch (op) {
+        case ISHMEMI_C_AMO_SET: __hip_atomic_store(p, v, kOrder, kScope); break;
+        case ISHMEMI_C_AMO_INC: (void) __hip_atomic_fetch_add(p, (U) 1, kOrder, kScope); break;
+        case ISHMEMI_C_AMO_ADD: (void) __hip_atomic_fetch_add(p, v, kOrder, kScope); break;
+        case ISHMEMI_C_AMO_AND: (void) __hip_atomic_fetch_and(p, v, kOrder, kScope); break;
+        case ISHMEMI_C_AMO_OR: (void) __hip_atomic_fetch_or(p, v, kOrder, kScope); break;
+        default: (void) __hip_atomic_fetch_xor(p, v, kOrder, kScope); break;
+    }
+}
+template <typename T>
+__device__ __forceinline__ void amo_n(int op, T *fetch, T *dest, T val, T cond, int pe)
+{
+    using U = ishmemi_amo::bits_t<T>;
+    const ishmemi_c_device_ctx_t *c = ctx();
+    if (!c || pe < 0 || pe >= c->npes) return;
+    const U old = amo_rmw<U>(op, (U *) peer_addr(c, dest, pe), __builtin_bit_cast(U, val), __builtin_bit_cast(U, cond));
+    *(U *) fetch = old;
+}
+}  // namespace ishmemx_dev
+ISHMEMI_AMO_DEFINE_ALL(__device__ inline, ishmemx_dev)
 
 #endif /* ISHMEM_AMD_ISHMEMX_DEVICE_H */

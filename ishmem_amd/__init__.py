@@ -609,6 +609,62 @@ for _tn in SYNC_TYPENAMES:
         setattr(_mod, _name, _f)
         SIGNAL_NAMES.append(_name)
 del _tn, _name, _f, _nbi, _bits, _is_test
+# ---- atomic memory operations (src/ishmem.h:331-640, src/amo.cpp) --------------------
+# atomic_<op>(dest, dtype, [value], [cond], pe) -> (status, fetched) for the 14 blocking operations and
+# atomic_<op>_nbi(fetch, dest, dtype, [value], [cond], pe) -> status for the 8 fetching ones.  `dtype`
+# is a name from DTYPES; values and results are the word's bits as Python integers (float / double
+# included).  `fetched` is 0 for a non-fetching operation.
+AMO_OPS = {"fetch": 0, "set": 1, "compare_swap": 2, "swap": 3, "fetch_inc": 4, "inc": 5, "fetch_add": 6, "add": 7,
+           "fetch_and": 8, "and": 9, "fetch_or": 10, "or": 11, "fetch_xor": 12, "xor": 13}
+AMO_FETCHING = ("fetch", "compare_swap", "swap", "fetch_inc", "fetch_add", "fetch_and", "fetch_or", "fetch_xor")
+_AMO_NO_VALUE = ("fetch", "fetch_inc", "inc")
+
+
+def amo(op: int, dtype: str, dest: int, value: int, cond: int, pe: int) -> tuple[int, int]:
+    """ishmemi_c_amo with the op code given as a number: (status, fetched bits)."""
+    f = ctypes.c_uint64(0)
+    rc = _L.ishmemi_c_amo(op, DTYPES.get(dtype, -1), dest or None, value & _U64, cond & _U64, pe, ctypes.byref(f))
+    return rc, f.value
+
+
+def amo_nbi(op: int, dtype: str, fetch: int, dest: int, value: int, cond: int, pe: int) -> int:
+    return _L.ishmemi_c_amo_nbi(op, DTYPES.get(dtype, -1), fetch or None, dest or None, value & _U64, cond & _U64, pe)
+
+
+def _make_amo(op: str, nbi: bool):
+    code = AMO_OPS[op]
+    if op == "compare_swap":
+        if nbi:
+            def fn(fetch: int, dest: int, dtype: str, cond: int, value: int, pe: int) -> int:
+                return amo_nbi(code, dtype, fetch, dest, value, cond, pe)
+        else:
+            def fn(dest: int, dtype: str, cond: int, value: int, pe: int) -> tuple[int, int]:
+                return amo(code, dtype, dest, value, cond, pe)
+    elif op in _AMO_NO_VALUE:
+        if nbi:
+            def fn(fetch: int, dest: int, dtype: str, pe: int) -> int:
+                return amo_nbi(code, dtype, fetch, dest, 0, 0, pe)
+        else:
+            def fn(dest: int, dtype: str, pe: int) -> tuple[int, int]:
+                return amo(code, dtype, dest, 0, 0, pe)
+    elif nbi:
+        def fn(fetch: int, dest: int, dtype: str, value: int, pe: int) -> int:
+            return amo_nbi(code, dtype, fetch, dest, value, 0, pe)
+    else:
+        def fn(dest: int, dtype: str, value: int, pe: int) -> tuple[int, int]:
+            return amo(code, dtype, dest, value, 0, pe)
+    return fn
+
+
+AMO_NAMES: list[str] = []
+for _op in AMO_OPS:
+    for _nbi in ((False, True) if _op in AMO_FETCHING else (False,)):
+        _name = f"atomic_{_op}{'_nbi' if _nbi else ''}"
+        _f = _make_amo(_op, _nbi)
+        _f.__name__ = _name
+        setattr(_mod, _name, _f)
+        AMO_NAMES.append(_name)
+del _op, _nbi, _name, _f
 API_NAMES: list[str] = []
 for _op, _tns in TYPENAMES_FOR_OP.items():
     for _tn in _tns:

@@ -366,4 +366,26 @@ struct WaitArgs {
 };
 hipError_t launch_signal_wait(const WaitArgs &a, hipStream_t s);
 
+// Atomic memory operations (kernels_amo.hip).  The codes are ISHMEMI_C_AMO_*.
+constexpr int kAmoFetch = 0, kAmoSet = 1, kAmoCompareSwap = 2, kAmoSwap = 3, kAmoFetchInc = 4, kAmoInc = 5,
+              kAmoFetchAdd = 6, kAmoAdd = 7, kAmoFetchAnd = 8, kAmoAnd = 9, kAmoFetchOr = 10, kAmoOr = 11,
+              kAmoFetchXor = 12, kAmoXor = 13, kAmoCount = 14;
+// The operations that return the word's old value (the ones with an _nbi form).
+__host__ __device__ constexpr bool amo_fetches(int op)
+{
+    return op == kAmoFetch || op == kAmoCompareSwap || op == kAmoSwap || op == kAmoFetchInc || op == kAmoFetchAdd ||
+           op == kAmoFetchAnd || op == kAmoFetchOr || op == kAmoFetchXor;
+}
+// One wave, one lane, one relaxed system-scope operation `op` on the `width`-byte (4 or 8) word at
+// `dest` (a PE's heap as mapped here) with the operand bits `value` (inc: 1) and, for compare_swap,
+// `cond`.  A fetching op stores the old value, `width` bytes, to `fetch_out` (device-accessible; may
+// be null) with a system-scope store.
+struct AmoArgs {
+    void *dest;
+    void *fetch_out;
+    uint64_t value, cond;
+    int op, width;
+};
+hipError_t launch_amo(const AmoArgs &a, hipStream_t s);
+
 }  // namespace ishmemi

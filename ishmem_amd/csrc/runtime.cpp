@@ -404,7 +404,9 @@ struct State {
     // call; s.mu is taken to validate, launch and release, never while waiting.
     hipStream_t wait_stream[kWaitSlots] = {};
     bool wait_busy[kWaitSlots] = {};
-    char *wait_host = nullptr, *wait_dev = nullptr;  // kWaitSlots lines of 64 B
+    // Line kWaitSlots of the same allocation: the blocking AMOs' fetched value (amo_impl; one word is
+    // enough, the call holds s.mu until host_wait returns).
+    char *wait_host = nullptr, *wait_dev = nullptr;  // kWaitSlots + 1 lines of 64 B
     // Stream of the previous collective: a collective enqueued on another stream first waits
     // for it, so epochs, flag rows and the staging region are used in call order.
     hipStream_t last_stream = nullptr;
@@ -1800,6 +1802,15 @@ int wait_args(const State &s, const char *what, void *ivar, int dt, int cmp, uin
     return 0;
 }
 
+// The pinned, mapped, coherent lines the wait kernels and the blocking AMOs report through.
+int wait_lines(State &s)
+{
+    if (s.wait_host) return 0;
+    HIP_TRY(hipHostMalloc((void **) &s.wait_host, (size_t) (kWaitSlots + 1) * 64, hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(hipHostGetDevicePointer((void **) &s.wait_dev, s.wait_host, 0));
+    return 0;
+}
+
 // Blocking host wait (budget 0), test or fetch (budget 1).  *status: kWaitMatched / kWaitNoMatch;
 // a timeout returns nonzero, counts as an error and still leaves the last value read in *value.
 int host_wait_until(const char *what, void *ivar, int dt, int cmp, uint64_t cmp_bits, uint64_t budget, uint64_t *value,
@@ -1815,10 +1826,7 @@ int host_wait_until(const char *what, void *ivar, int dt, int cmp, uint64_t cmp_
     {
         std::lock_guard<std::mutex> lk(s.mu);
         if (wait_args(s, what, ivar, dt, cmp, cmp_bits, a)) return 1;
-        if (!s.wait_host) {
-            HIP_TRY(hipHostMalloc((void **) &s.wait_host, (size_t) kWaitSlots * 64, hipHostMallocMapped | hipHostMallocCoherent));
-            HIP_TRY(hipHostGetDevicePointer((void **) &s.wait_dev, s.wait_host, 0));
-        }
+        if (wait_lines(s)) return 1;
         for (int k = 0; k < kWaitSlots && slot < 0; ++k)
             if (!s.wait_busy[k]) slot = k;
         if (slot < 0) return fail(std::string(what) + ": more than " + std::to_string(kWaitSlots) + " host threads are waiting at once");
@@ -1894,6 +1902,87 @@ int wait_until_on_stream_impl(void *ivar, int dt, int cmp, uint64_t cmp_bits, ui
     a.status_out = ret;
     a.err = s.err_dev + kMaxTeams;
     HIP_TRY(launch_signal_wait(a, st));
+    return 0;
+}
+
+// ---------------- atomic memory operations ----------------------------------------
+// ishmem_<TN>_atomic_<op>[_nbi] (src/amo.cpp, src/amo_impl.h): one amo_kernel launch per call
+// (kernels_amo.hip).  Blocking: the null stream, then host_wait; the fetched value comes back through
+// the pinned line behind the wait slots.  _nbi: rma_stream, rma_pending, so quiet / quiet_on_stream /
+// barrier_all cover it and *fetch is defined after them.
+// Ordering against puts (§3d clause 1): rma_stream is a non-blocking stream, which the null stream
+// does NOT serialise behind.  A blocking AMO issued while _nbi work is pending therefore makes the
+// null stream wait for an event recorded on rma_stream before its kernel is enqueued; after
+// ishmem_quiet nothing is pending and blocking puts have completed before they return.  An _nbi AMO is
+// enqueued on rma_stream itself, behind every earlier _nbi put.  Either way the AMO kernel starts
+// after the earlier puts' kernels have ended (their write-through stores acknowledged).
+const char *const kAmoName[kAmoCount] = {"fetch", "set", "compare_swap", "swap", "fetch_inc", "inc", "fetch_add",
+                                         "add", "fetch_and", "and", "fetch_or", "or", "fetch_xor", "xor"};
+
+int amo_impl(bool nbi, int op, int dt, void *fetch, void *dest, uint64_t value, uint64_t cond, int pe, uint64_t *fetched)
+{
+    State &s = S();
+    std::lock_guard<std::mutex> lk(s.mu);
+    if (op < 0 || op >= kAmoCount) {
+        if (!s.initialized) return fail(std::string(nbi ? "atomic_nbi" : "atomic") + ": not initialized");
+        return fail(std::string(nbi ? "atomic_nbi" : "atomic") + ": op " + std::to_string(op) + " is not one of ISHMEMI_C_AMO_*");
+    }
+    const std::string what = std::string("atomic_") + kAmoName[op] + (nbi ? "_nbi" : "");
+    if (!s.initialized) return fail(what + ": not initialized");
+    if (nbi && !amo_fetches(op)) return fail(what + ": only the fetching operations have an _nbi form");
+    if (pe < 0 || pe >= s.npes)
+        return fail(what + ": pe " + std::to_string(pe) + " outside [0, " + std::to_string(s.npes) + ")");
+    int width = 0;
+    switch (dt) {
+        case ISHMEMI_DT_INT32: case ISHMEMI_DT_UINT32: width = 4; break;
+        case ISHMEMI_DT_INT64: case ISHMEMI_DT_UINT64: width = 8; break;
+        case ISHMEMI_DT_FLOAT: case ISHMEMI_DT_DOUBLE:
+            if (op != kAmoFetch && op != kAmoSet && op != kAmoSwap)
+                return fail(what + ": float and double take fetch, set and swap only");
+            width = dt == ISHMEMI_DT_FLOAT ? 4 : 8;
+            break;
+        default:
+            return fail(what + ": dtype " + std::to_string(dt) + " is not a 32- or 64-bit integer type, float or double");
+    }
+    if (const char *e = sync_word_error(s, dest, (size_t) width)) return fail(what + ": dest" + e);
+    char *remote = translate(s, dest, pe);
+    if (!remote) return fail(what + ": heap of PE " + std::to_string(pe) + " not mapped");
+    AmoArgs a{};
+    a.dest = remote;
+    a.op = op;
+    a.width = width;
+    a.value = (op == kAmoFetchInc || op == kAmoInc) ? 1 : value;
+    a.cond = cond;
+    if (nbi) {
+        if (!fetch) return fail(what + ": fetch is null");
+        if ((uintptr_t) fetch % (size_t) width) return fail(what + ": fetch is not aligned to its width");
+        a.fetch_out = device_view(s, fetch);
+        if (!a.fetch_out)
+            return fail(what + ": fetch is not device-accessible (heap, device or pinned host memory; pageable host "
+                        "memory is not accepted by _nbi forms)");
+        int rc = 0;
+        hipStream_t st = rma_kind_stream(s, kRmaNbi, nullptr, rc);
+        if (rc) return 1;
+        HIP_TRY(launch_amo(a, st));
+        s.rma_pending = true;
+        return 0;
+    }
+    volatile uint64_t *hv = nullptr;
+    if (amo_fetches(op)) {
+        if (wait_lines(s)) return 1;
+        hv = (volatile uint64_t *) (s.wait_host + (size_t) kWaitSlots * 64);
+        *hv = 0;
+        a.fetch_out = s.wait_dev + (size_t) kWaitSlots * 64;
+    }
+    if (s.rma_pending) {
+        // The null stream does not wait for a non-blocking stream by itself (see above).
+        if (!s.rma_ev) HIP_TRY(hipEventCreateWithFlags(&s.rma_ev, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(s.rma_ev, s.rma_stream));
+        HIP_TRY(hipStreamWaitEvent(0, s.rma_ev, 0));
+    }
+    HIP_TRY(launch_amo(a, 0));
+    if (host_wait(s, 0)) return 1;
+    if (fetched) *fetched = hv ? *hv : 0;
     return 0;
 }
 
@@ -3445,6 +3534,16 @@ int ishmemi_c_test(void *ivar, int dtype, int cmp, uint64_t cmp_value_bits, int 
     const int rc = host_wait_until("test", ivar, dtype, cmp, cmp_value_bits, 1, nullptr, &status);
     if (result) *result = (rc == 0 && status == kWaitMatched) ? 1 : 0;
     return rc;
+}
+
+int ishmemi_c_amo(int op, int dtype, void *dest, uint64_t value_bits, uint64_t cond_bits, int pe, uint64_t *fetched_bits)
+{
+    return amo_impl(false, op, dtype, nullptr, dest, value_bits, cond_bits, pe, fetched_bits);
+}
+
+int ishmemi_c_amo_nbi(int op, int dtype, void *fetch, void *dest, uint64_t value_bits, uint64_t cond_bits, int pe)
+{
+    return amo_impl(true, op, dtype, fetch, dest, value_bits, cond_bits, pe, nullptr);
 }
 
 int ishmemi_c_wait_until_on_stream(void *ivar, int dtype, int cmp, uint64_t cmp_value_bits, uint64_t *value, int *ret,
