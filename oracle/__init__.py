@@ -55,6 +55,10 @@ def lib() -> ctypes.CDLL:
         L.oracle_fill_random.argtypes = [i, ctypes.c_uint64, ctypes.c_double, ctypes.c_double, sz, vp]
         L.oracle_fill_random.restype = None
         L.oracle_valid.argtypes = [i, i]
+        L.oracle_fill_special.argtypes = [i, i, i, sz, vp]
+        L.oracle_special_rows.argtypes = []
+        L.oracle_special_period.argtypes = [i]
+        L.oracle_special_period.restype = sz
         _lib = L
     return _lib
 
@@ -145,6 +149,23 @@ def fill_random(dt: int, seed: int, n: int, lo: float = -1.0, hi: float = 1.0) -
     return out
 
 
+def fill_special(dt: int, member: int, npes: int, n: int) -> np.ndarray:
+    """Member `member`'s special-value source (oracle_fill_special): signed zeros, NaN, infinities,
+    overflow and subnormal rows rotated through the members; float / double only."""
+    out = np.zeros(n, dtype=NP[dt])
+    if lib().oracle_fill_special(dt, member, npes, n, out.ctypes.data):
+        raise ValueError("fill_special: float / double and 0 <= member < npes only")
+    return out
+
+
+def special_rows() -> int:
+    return int(lib().oracle_special_rows())
+
+
+def special_period(npes: int) -> int:
+    return int(lib().oracle_special_period(npes))
+
+
 def fp_tolerance(dt: int, op: int, srcs: list[np.ndarray], ref: np.ndarray) -> np.ndarray:
     """Order-independent error bound for FP sum/prod of p terms (SURVEY.md §8c parity rule):
     sum: (p-1) * u * sum_i |x_i|;  prod: (p-1) * u * |ref| * (1 + tiny);  u = 2^-24 / 2^-53.
@@ -168,7 +189,7 @@ def scan_fold(dt: int, srcs: list[np.ndarray], me: int, inclusive: bool) -> np.n
     t = NP[dt]
     out = np.zeros_like(np.asarray(srcs[0], dtype=t))
     last = me + 1 if inclusive else me
-    with np.errstate(over="ignore"):
+    with np.errstate(over="ignore", invalid="ignore"):  # inf - inf is part of the contract
         for k in range(last):
             out = np.asarray(srcs[k], dtype=t).copy() if k == 0 else (out + np.asarray(srcs[k], dtype=t)).astype(t)
     return out

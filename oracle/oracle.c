@@ -496,3 +496,120 @@ void oracle_fill_random(int dt, uint64_t seed, double lo, double hi, size_t n, v
         }
     }
 }
+
+/* ---------------------------------------------------------------------------------------------
+ * Special values (DESIGN.md "Special values"): a table of rows, one value per member in each,
+ * tiled over the n elements.  Every row appears npes times in a row, rotated by one member each
+ * time, so a row's special entry sits in member 0 (the fold's start), in every middle member and in
+ * the last one.  The period is padded to an odd length with one row of ordinary values, so for
+ * n >= 4 * period every row lands on every lane of a 16-B item.
+ * ------------------------------------------------------------------------------------------- */
+enum { SV_ALL, SV_ONE, SV_TWO };
+enum {
+    V_PZ, V_NZ, V_P1, V_N1, V_HALF, V_FIN, V_NFIN, V_NAN, V_PINF, V_NINF, V_MAX, V_NMAX, V_MINSUB,
+    V_NMINSUB, V_MAXSUB, V_MINNORM
+};
+struct sv_row {
+    int kind, a, b, fill; /* ALL: a everywhere; ONE: a among fill; TWO: a then b among fill */
+};
+/* Ordered so that every prefix of the table stays within the caps tests/special_values.py sets on
+ * NaN results (a quarter of the elements) and on zeros of either sign (a tenth), small n included. */
+static const struct sv_row SV_ROWS[] = {
+    {SV_ALL, V_NZ, 0, 0},               /* all -0: sum -0, max / min -0 */
+    {SV_ONE, V_NZ, 0, V_P1},            /* -0 among 1.0 */
+    {SV_ONE, V_PINF, 0, V_FIN},         /* +inf among finite */
+    {SV_ALL, V_MINSUB, 0, 0},           /* smallest subnormal everywhere: the sum is exact */
+    {SV_ONE, V_NAN, 0, V_FIN},          /* one quiet NaN: missing for max / min, NaN for sum / prod */
+    {SV_ONE, V_NZ, 0, V_N1},            /* -0 among -1.0 */
+    {SV_ALL, V_PZ, 0, 0},               /* all +0 */
+    {SV_ONE, V_NINF, 0, V_NFIN},        /* -inf among negative finite */
+    {SV_TWO, V_PINF, V_PZ, V_FIN},      /* inf x 0: prod NaN */
+    {SV_ALL, V_MAX, 0, 0},              /* sum and prod overflow to +inf */
+    {SV_ONE, V_PZ, 0, V_NZ},            /* one +0 among -0: sum +0, max / min a zero of either sign */
+    {SV_TWO, V_PINF, V_NINF, V_FIN},    /* +inf with -inf: sum NaN */
+    {SV_ALL, V_NMINSUB, 0, 0},
+    {SV_ALL, V_NINF, 0, 0},             /* all -inf: max stays -inf */
+    {SV_TWO, V_MINSUB, V_NMINSUB, V_PZ}, /* cancels to +0 */
+    {SV_ONE, V_MAX, 0, V_FIN},
+    {SV_ALL, V_NAN, 0, 0},              /* all NaN: max / min stay NaN */
+    {SV_ALL, V_NMAX, 0, 0},             /* sum overflows to -inf */
+    {SV_TWO, V_MAXSUB, V_MINSUB, V_PZ}, /* the sum lands on the smallest normal; prod underflows to 0 */
+    {SV_ALL, V_PINF, 0, 0},
+    {SV_TWO, V_NINF, V_NZ, V_FIN},      /* -inf x -0: prod NaN */
+    {SV_ONE, V_NZ, 0, V_PZ},            /* one -0 among +0 */
+    {SV_ONE, V_MINNORM, 0, V_HALF},     /* prod underflows gradually into the subnormals */
+    {SV_TWO, V_NAN, V_PINF, V_FIN},     /* NaN with +inf */
+    {SV_ONE, V_MINSUB, 0, V_NZ},        /* a subnormal with -0 */
+    {SV_ONE, V_NMINSUB, 0, V_PZ},
+    {SV_ALL, V_NFIN, 0, 0},             /* ordinary values, the members' differing */
+};
+#define SV_NROWS ((int) (sizeof(SV_ROWS) / sizeof(SV_ROWS[0])))
+
+int oracle_special_rows(void) { return SV_NROWS; }
+
+size_t oracle_special_period(int npes)
+{
+    if (npes < 1) return 0;
+    const size_t body = (size_t) SV_NROWS * (size_t) npes;
+    return body | 1; /* even: one padding row more */
+}
+
+/* Bit pattern of value `code` for member `member`; the quiet NaN carries a payload. */
+static uint64_t sv_bits(int dt, int code, int member)
+{
+    const double fin = 0.5 + 0.125 * (double) (member & 7);
+    double v = 0.0;
+    switch (code) {
+        case V_PZ: v = 0.0; break;
+        case V_NZ: v = -0.0; break;
+        case V_P1: v = 1.0; break;
+        case V_N1: v = -1.0; break;
+        case V_HALF: v = 0.5; break;
+        case V_FIN: v = fin; break;
+        case V_NFIN: v = -fin; break;
+        case V_NAN: return dt == OD_FLOAT ? 0x7FC12345ull : 0x7FF8000000012345ull;
+        case V_PINF: v = INFINITY; break;
+        case V_NINF: v = -INFINITY; break;
+        case V_MAX: return dt == OD_FLOAT ? 0x7F7FFFFFull : 0x7FEFFFFFFFFFFFFFull;
+        case V_NMAX: return dt == OD_FLOAT ? 0xFF7FFFFFull : 0xFFEFFFFFFFFFFFFFull;
+        case V_MINSUB: return 1ull;
+        case V_NMINSUB: return dt == OD_FLOAT ? 0x80000001ull : 0x8000000000000001ull;
+        case V_MAXSUB: return dt == OD_FLOAT ? 0x007FFFFFull : 0x000FFFFFFFFFFFFFull;
+        case V_MINNORM: return dt == OD_FLOAT ? 0x00800000ull : 0x0010000000000000ull;
+    }
+    uint64_t b = 0;
+    if (dt == OD_FLOAT) {
+        const float f = (float) v;
+        uint32_t w;
+        memcpy(&w, &f, 4);
+        b = w;
+    } else {
+        memcpy(&b, &v, 8);
+    }
+    return b;
+}
+
+int oracle_fill_special(int dt, int member, int npes, size_t n, void *out)
+{
+    if ((dt != OD_FLOAT && dt != OD_DOUBLE) || npes < 1 || member < 0 || member >= npes) return 1;
+    const size_t period = oracle_special_period(npes);
+    for (size_t i = 0; i < n; ++i) {
+        const size_t t = i % period;
+        int code = V_FIN; /* the padding row */
+        if (t < (size_t) SV_NROWS * (size_t) npes) {
+            const struct sv_row *r = &SV_ROWS[t / (size_t) npes];
+            const int rot = (int) (t % (size_t) npes);
+            if (r->kind == SV_ALL || member == rot) code = r->a;
+            else if (r->kind == SV_TWO && member == (rot + 1) % npes) code = r->b;
+            else code = r->fill;
+        }
+        const uint64_t b = sv_bits(dt, code, member);
+        if (dt == OD_FLOAT) {
+            const uint32_t w = (uint32_t) b;
+            memcpy((char *) out + 4 * i, &w, 4);
+        } else {
+            memcpy((char *) out + 8 * i, &b, 8);
+        }
+    }
+    return 0;
+}

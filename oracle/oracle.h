@@ -75,6 +75,15 @@ int oracle_pattern_check(int family, int op, int dt, int npes, size_t nelems, vo
 /* xorshift64* fill (SURVEY.md §8d seeds): ints full range, fp uniform [lo, hi). */
 void oracle_fill_random(int dt, uint64_t seed, double lo, double hi, size_t n, void *out);
 
+/* Special-value inputs of the FP reductions and scans (float / double only): member `member`'s
+ * n elements of a team of `npes`.  A table of oracle_special_rows() rows (signed zeros, a quiet NaN
+ * with a payload, infinities, the largest finite value, subnormals, with the fillers sum and prod
+ * need) is tiled over the elements; every row appears npes times, its special entry rotated through
+ * the members, and the period (oracle_special_period) is odd.  Returns nonzero for other dtypes. */
+int oracle_fill_special(int dt, int member, int npes, size_t n, void *out);
+int oracle_special_rows(void);
+size_t oracle_special_period(int npes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,7 +26,10 @@ SCAN_TYPES = {"uint8": 1, "int16": 2, "float": 4, "double": 8}
 SCAN_TYPES_WIDE = {"float": 4, "uint8": 1}  # the 8-PE handshake / phased runs
 TEAM_SCAN_TYPES = {"float": 4, "int16": 2}
 
-ScanCase = namedtuple("ScanCase", "dtype inclusive n so do inplace")
+# kind: "random" (coll_worker.scan_input) or "special" (member j's source from oracle.fill_special:
+# NaN, infinities, signed zeros, overflow, subnormals; checked under special_values.compare_scan).
+ScanCase = namedtuple("ScanCase", "dtype inclusive n so do inplace kind", defaults=("random",))
+SPECIAL_SCAN_TYPES = ("float", "double")  # oracle.fill_special fills FP types only
 CollCase = namedtuple("CollCase", "form B so do root inplace idx")
 
 
@@ -112,6 +115,25 @@ def scan_cases(p: int, types=SCAN_TYPES, thin: bool = False) -> list[ScanCase]:
                 for inclusive in ([(si + pi) % 2 == 0] if thin else [True, False]):
                     out.append(ScanCase(dtype, inclusive, n, so, do, inplace))
     return out
+
+
+def special_scan_cases(p: int, types=SCAN_TYPES) -> list[ScanCase]:
+    """The FP sum scans once more over the special-value table: every (size x offset pair) of the
+    type, inclusive or exclusive by (size index + pair index) mod 2, so each offset pair runs both
+    ways (at alternate sizes) and every cell of every path is met again."""
+    out = []
+    for dtype in SPECIAL_SCAN_TYPES:
+        if dtype not in types:
+            continue
+        es = types[dtype]
+        for si, n in enumerate(scan_sizes(es, p)):
+            for pi, (so, do, inplace) in enumerate(scan_pairs(es)):
+                out.append(ScanCase(dtype, (si + pi) % 2 == 0, n, so, do, inplace, "special"))
+    return out
+
+
+def special_team_scan_cases(p: int) -> list[ScanCase]:
+    return [c._replace(kind="special") for c in team_scan_cases(p) if c.dtype in SPECIAL_SCAN_TYPES]
 
 
 def team_scan_cases(p: int) -> list[ScanCase]:

@@ -4,7 +4,9 @@
 Every dest sits in the heap as [64 B guard | payload | 64 B guard], uploaded as 0xA5 before the call
 (an in-place source goes into the payload afterwards); the whole block is downloaded and compared
 bit-exactly: scans against oracle.scan_fold (team-order linear fold, FP included), the copies
-against numpy concatenations of seeded random bytes.  Every case is first checked against the path
+against numpy concatenations of seeded random bytes.  The FP sum scans run once more over the
+special-value table (oracle.fill_special; DESIGN.md "Special values"), their payload compared under
+special_values.compare_scan.  Every case is first checked against the path
 its environment is meant to reach (tests/coll_cases.py scan_path / collect_path with the live
 thresholds), so no path goes untested in silence.  Failures are returned as strings through the
 queue.
@@ -18,6 +20,7 @@ import traceback
 import numpy as np
 
 from tests import coll_cases as cc
+from tests import special_values as sv
 
 GUARD = cc.GUARD
 PRESET = 0x7F7F7F7F  # *ret before an on-stream call
@@ -109,14 +112,29 @@ def run(pe: int, npes: int, key: str, scenarios: list[str], q, env: dict | None 
         # ---- scans ---------------------------------------------------------------------------
         def scan_prepare(c, me, p, seed, dbase, sbase):
             es = cc.SCAN_TYPES[c.dtype]
-            ins = [scan_input(c.dtype, seed, j, c.n) for j in range(p)]
+            if c.kind == "special":
+                ins = [oracle.fill_special(DT[c.dtype], j, p, c.n) for j in range(p)]
+            else:
+                ins = [scan_input(c.dtype, seed, j, c.n) for j in range(p)]
             dst = stage(dbase, c.do, c.n * es)
             src = dst if c.inplace else sbase + c.so
             hip.upload(src, ins[me])
             want = oracle.scan_fold(DT[c.dtype], ins, me, c.inclusive)
-            return dst, src, want
+            return dst, src, want, ins
+
+        def check_special(tag, base, c, ins, me):
+            """Guards bit-exact, the payload under the special-value comparison rule (NaN where the
+            team-order fold is NaN, the oracle's bits elsewhere)."""
+            nb = c.n * cc.SCAN_TYPES[c.dtype]
+            got = hip.download(base + c.do, 2 * GUARD + nb, np.uint8)
+            if not (np.array_equal(got[:GUARD], guard) and np.array_equal(got[GUARD + nb:], guard)):
+                fail(f"{tag}: guard bytes written")
+            payload = got[GUARD:GUARD + nb].copy().view(oracle.NP[DT[c.dtype]])
+            for m in sv.compare_scan(DT[c.dtype], ins, me, c.inclusive, payload)[:2]:
+                fail(f"{tag}: {m}")
 
         def scan_tag(c, p, what=""):
+            what = what + ("special values " if c.kind == "special" else "")
             return (f"{what}{'in' if c.inclusive else 'ex'}scan {c.dtype} p={p} n={c.n} "
                     f"{'in place +' + str(c.do) if c.inplace else 's+' + str(c.so) + ' d+' + str(c.do)}")
 
@@ -136,19 +154,22 @@ def run(pe: int, npes: int, key: str, scenarios: list[str], q, env: dict | None 
             tag = scan_tag(c, p, what)
             if not scan_path_check(c, p, tag):
                 return
-            dst, src, want = scan_prepare(c, me, p, seed, dbuf, sbuf)
+            dst, src, want, ins = scan_prepare(c, me, p, seed, dbuf, sbuf)
             rc = ish.scan(c.dtype, c.inclusive, dst, src, c.n, team)
             ran["scan"] += 1
             if rc:
                 fail(f"{tag}: rc={rc} {ish.last_error()}")
                 return
-            check(tag, dbuf, c.do, want)
+            if c.kind == "special":
+                check_special(tag, dbuf, c, ins, me)
+            else:
+                check(tag, dbuf, c.do, want)
 
         def scan_types():
             return cc.SCAN_TYPES_WIDE if npes == 8 and envname != "granule" else cc.SCAN_TYPES
 
         if "scan" in scenarios:
-            cases = cc.scan_cases(npes, scan_types(), thin="thin" in scenarios)
+            cases = cc.scan_cases(npes, scan_types(), thin="thin" in scenarios) + cc.special_scan_cases(npes, scan_types())
             for i, c in enumerate(cases):
                 scan_one(c, W, pe, npes, 10_000 + i)
             if ran["scan"] != len(cases) and not fails:
@@ -161,7 +182,8 @@ def run(pe: int, npes: int, key: str, scenarios: list[str], q, env: dict | None 
             ish.set_param("direct_p2", 0)
             if int(ish.get_param("fold_limit_bytes")) != 0:
                 fail(f"direct_p2 0: fold_limit_bytes {ish.get_param('fold_limit_bytes')}")
-            for i, c in enumerate(cc.scan_cases(npes, scan_types(), thin="thin" in scenarios)):
+            for i, c in enumerate(cc.scan_cases(npes, scan_types(), thin="thin" in scenarios)
+                                  + cc.special_scan_cases(npes, scan_types())):
                 if not c.inplace:
                     scan_one(c, W, pe, npes, 200_000 + i, "nodirect ")
             ish.ishmem_barrier_all()
@@ -180,7 +202,7 @@ def run(pe: int, npes: int, key: str, scenarios: list[str], q, env: dict | None 
                 fail(f"{tag}: fewer than three segments")
             big = ish.ishmem_align(256, c.n * 4 + 2 * GUARD + 256)
             if scan_path_check(c, npes, tag, seg):
-                dst, src, want = scan_prepare(c, pe, npes, 300_000, big, big)
+                dst, src, want, _ = scan_prepare(c, pe, npes, 300_000, big, big)
                 rc = ish.scan(c.dtype, c.inclusive, dst, src, c.n, W)
                 if rc:
                     fail(f"{tag}: rc={rc} {ish.last_error()}")
@@ -276,7 +298,7 @@ def run(pe: int, npes: int, key: str, scenarios: list[str], q, env: dict | None 
                 if idx < 0:
                     return
                 if "scan_teams" in scenarios:
-                    for i, c in enumerate(cc.team_scan_cases(size)):
+                    for i, c in enumerate(cc.team_scan_cases(size) + cc.special_team_scan_cases(size)):
                         scan_one(c, t, idx, size, 700_000 + 1000 * ti + i, f"team {name}: ")
                 if "coll_teams" in scenarios:
                     for c in cc.coll_cases(size, cc.TEAM_COLL_SIZES, cc.TEAM_COLL_OFFSETS):
@@ -314,7 +336,7 @@ def run(pe: int, npes: int, key: str, scenarios: list[str], q, env: dict | None 
                 if form == "scan":
                     tag = scan_tag(c, npes, "on stream ")
                     ok = scan_path_check(c, npes, tag)
-                    dst, src, want = scan_prepare(c, pe, npes, 900_000 + k, db, sb)
+                    dst, src, want, _ = scan_prepare(c, pe, npes, 900_000 + k, db, sb)
                     counts = None
                 else:
                     tag = coll_tag(c, npes, "on stream ")

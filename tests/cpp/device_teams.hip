@@ -8,6 +8,10 @@
 //             {0, sizeof(T), 16 - sizeof(T)}^2, so the element-wise arms run as the whole body
 //   checker   oracle_reduce_fold / oracle_combine over seeded oracle_fill_random inputs in team
 //             order, bit-exact for every type; closed-form bytes for collect / broadcast / alltoall
+//   special   NaN, infinities, signed zeros, overflow and subnormals (oracle_fill_special) through
+//             the FP reduces and sum scans, compared by special_rule(): NaN where the team-order
+//             fold is NaN, a zero of either sign for max / min over zeros of both signs, the
+//             oracle's bits everywhere else
 // A device collective that returns non-zero on a member (a barrier timed out) leaves the members
 // out of step: the program prints the FAIL line and stops there.
 // Launch: ISHMEM_PE=<pe> ISHMEM_NPES=<n> ISHMEM_DEVICE=0 ISHMEM_BOOTSTRAP_KEY=<k> ./device_teams
@@ -16,6 +20,7 @@
 #include <unistd.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <type_traits>
@@ -287,6 +292,88 @@ static void reduce_case(const Team &t, int ti, int mode, int block, size_t n, in
     if (r != 0) stop("a device reduce returned non-zero on a member");
 }
 
+// The special-value comparison rule (DESIGN.md "Special values"), written once: `got` against the
+// team-order fold `want` of the members `src[0 .. nsrc)`.  An element that is NaN in the fold must be
+// NaN (any payload, any sign); a max / min that is zero while the column's non-NaN zeros carry both
+// signs may be a zero of either sign (glibc and the GPU may differ); every other element must have
+// the fold's bits.  A team of one copies: bits throughout.  Elements that meet a soft rule are
+// copied into `want`, so check_block then compares the whole block, guards included.  Returns the
+// number of elements that took a soft rule above the caps tests/special_values.py sets (a quarter
+// NaN, a tenth either-zero), which the table never reaches: 0 for a sound case.
+template <typename T>
+static size_t special_rule(int op, const std::vector<std::vector<T>> &src, size_t nsrc, std::vector<T> &want,
+                           const unsigned char *got_bytes)
+{
+    const size_t n = want.size();
+    size_t nan = 0, zero = 0;
+    for (size_t i = 0; i < n; ++i) {
+        T got;
+        memcpy(&got, got_bytes + i * sizeof(T), sizeof(T));
+        if (nsrc < 2) continue;
+        if (std::isnan(want[i])) {
+            ++nan;
+            if (std::isnan(got)) want[i] = got;
+            continue;
+        }
+        if ((op == OR_MAX || op == OR_MIN) && want[i] == 0) {
+            bool pos = false, neg = false;
+            for (size_t j = 0; j < nsrc; ++j)
+                if (src[j][i] == 0) (std::signbit(src[j][i]) ? neg : pos) = true;
+            if (pos && neg) {
+                ++zero;
+                if (got == 0) want[i] = got;
+            }
+        }
+    }
+    return (4 * nan > n ? nan : 0) + (10 * zero > n ? zero : 0);
+}
+
+// A reduce over the special-value table: member j's source from oracle_fill_special, the expected
+// values from oracle_reduce_fold, compared by special_rule.
+template <typename T, int OPC>
+static void reduce_special_case(const Team &t, int ti, int mode, int block, size_t n, int d, int s)
+{
+    constexpr int ODT = TI<T>::odt;
+    std::vector<std::vector<T>> src((size_t) t.size, std::vector<T>(n));
+    std::vector<const void *> ptrs((size_t) t.size);
+    for (int j = 0; j < t.size; ++j) {
+        if (oracle_fill_special(ODT, j, t.size, n, src[(size_t) j].data())) stop("oracle_fill_special failed");
+        ptrs[(size_t) j] = src[(size_t) j].data();
+    }
+    std::vector<T> want(n);
+    oracle_reduce_fold(OPC, ODT, ptrs.data(), t.size, 0, want.data(), n);
+    const size_t nb = n * sizeof(T), len = block_len(nb);
+    fill_block(len);
+    T *dst = (T *) (db + kGuard + d);
+    const T *sp = (const T *) (sb + kGuard + s);
+    (void) hipMemcpy((void *) sp, src[(size_t) t.me].data(), nb, hipMemcpyHostToDevice);
+    hipLaunchKernelGGL((reduce_kernel<T, OPC>), dim3(1), dim3(mode == 0 ? block : mode == 1 ? 256 : 1), 0, 0, t.h, dst,
+                       sp, n, mode, rc_of(len));
+    const int r = finish(len);
+    const size_t capped = special_rule<T>(OPC, src, (size_t) t.size, want, hostblk.data() + kGuard + d);
+    const size_t bad = check_block(len, kGuard + d, want.data(), nb) + capped;
+    if (r != 0 || bad) fail("reduce-special", mode, block, t, TI<T>::name, kOpName[OPC], n, d, s, r, bad);
+    if (r != 0) stop("a device reduce returned non-zero on a member");
+}
+
+// max / min / sum / prod over the table in the block, tile and one-work-item modes, at n = E + 1 and
+// 2 * 64 * 4 * E + E + 1, aligned and with dest and source on different phases.
+template <typename T>
+static void reduce_special_sweep(const Team &t, int ti)
+{
+    const size_t E = 16 / sizeof(T);
+    const int a = (int) sizeof(T), b = 16 - (int) sizeof(T);
+    for (size_t n : {E + 1, 2 * 64 * 4 * E + E + 1})
+        for (const auto &p : {std::pair<int, int>{0, 0}, std::pair<int, int>{a, b}})
+            for (int mode = 0; mode < 3; ++mode) {
+                const int block = mode == 0 ? (n > E + 1 ? 256 : 64) : mode == 1 ? 256 : 1;
+                reduce_special_case<T, OR_MAX>(t, ti, mode, block, n, p.first, p.second);
+                reduce_special_case<T, OR_MIN>(t, ti, mode, block, n, p.first, p.second);
+                reduce_special_case<T, OR_SUM>(t, ti, mode, block, n, p.first, p.second);
+                reduce_special_case<T, OR_PROD>(t, ti, mode, block, n, p.first, p.second);
+            }
+}
+
 // One reduce case with the op chosen at run time (FP types have max, min, sum and prod only).
 template <typename T>
 static void reduce_op_case(int op, const Team &t, int ti, int mode, int block, size_t n, int d, int s, bool inplace)
@@ -357,19 +444,29 @@ static void reduce_suite(const Team &t, int ti)
     reduce_inplace_sweep<float, OR_MIN>(t, ti);
     reduce_inplace_sweep<double, OR_SUM>(t, ti);
     reduce_inplace_sweep<int32_t, OR_PROD>(t, ti);
+    // NaN, infinities, signed zeros, overflow and subnormals.
+    reduce_special_sweep<float>(t, ti);
+    reduce_special_sweep<double>(t, ti);
 }
 
 // Prefix sums: a plain left-to-right fold in T over members 0..me (inclusive) or 0..me-1
 // (exclusive; member 0 gets zeros).  The first term passes through unchanged: member 0's first
-// FP element is -0.0 and must come back as -0.0.
+// FP element is -0.0 and must come back as -0.0.  special (FP types): member j's source from
+// oracle_fill_special instead, the result compared by special_rule.
 template <typename T>
-static void scan_case(const Team &t, int ti, int mode, int block, size_t n, int d, int s, bool incl)
+static void scan_case(const Team &t, int ti, int mode, int block, size_t n, int d, int s, bool incl, bool special = false)
 {
     constexpr int ODT = TI<T>::odt;
     std::vector<std::vector<T>> src((size_t) t.size, std::vector<T>(n));
-    for (int j = 0; j < t.size; ++j)
-        oracle_fill_random(ODT, case_seed(3, ti, ODT, incl, n, mode, block, d, s, j), -1.0, 1.0, n, src[(size_t) j].data());
-    if constexpr (ODT >= OD_FLOAT) src[0][0] = (T) -0.0;
+    for (int j = 0; j < t.size; ++j) {
+        if (special) {
+            if (oracle_fill_special(ODT, j, t.size, n, src[(size_t) j].data())) stop("oracle_fill_special failed");
+        } else {
+            oracle_fill_random(ODT, case_seed(3, ti, ODT, incl, n, mode, block, d, s, j), -1.0, 1.0, n, src[(size_t) j].data());
+        }
+    }
+    if constexpr (ODT >= OD_FLOAT)
+        if (!special) src[0][0] = (T) -0.0;
     const int last = incl ? t.me : t.me - 1;
     std::vector<T> want(n, T());
     if (last >= 0) {
@@ -384,8 +481,13 @@ static void scan_case(const Team &t, int ti, int mode, int block, size_t n, int 
     hipLaunchKernelGGL(scan_kernel<T>, dim3(1), dim3(mode == 0 ? block : mode == 1 ? 256 : 1), 0, 0, t.h, dst, sp, n,
                        mode, (int) incl, rc_of(len));
     const int r = finish(len);
-    const size_t bad = check_block(len, kGuard + d, want.data(), nb);
-    if (r != 0 || bad) fail(incl ? "sum_inscan" : "sum_exscan", mode, block, t, TI<T>::name, "sum", n, d, s, r, bad);
+    size_t capped = 0;
+    if constexpr (ODT >= OD_FLOAT)
+        if (special && last >= 1) capped = special_rule<T>(OR_SUM, src, (size_t) last + 1, want, hostblk.data() + kGuard + d);
+    const size_t bad = check_block(len, kGuard + d, want.data(), nb) + capped;
+    if (r != 0 || bad)
+        fail(special ? (incl ? "sum_inscan-special" : "sum_exscan-special") : incl ? "sum_inscan" : "sum_exscan", mode, block, t,
+             TI<T>::name, "sum", n, d, s, r, bad);
     if (r != 0) stop("a device scan returned non-zero on a member");
 }
 
@@ -403,6 +505,13 @@ static void scan_sweep(const Team &t, int ti)
                 scan_case<T>(t, ti, 1, 256, n, p.first, p.second, incl);
             }
             scan_case<T>(t, ti, 2, 1, n, p.first, p.second, true);  // ishmem_<T>_sum_inscan by one work-item
+            if constexpr (std::is_floating_point_v<T>) {  // the special-value table, every group
+                for (bool incl : {true, false}) {
+                    scan_case<T>(t, ti, 0, n > E + 1 ? 256 : 64, n, p.first, p.second, incl, true);
+                    scan_case<T>(t, ti, 1, 256, n, p.first, p.second, incl, true);
+                }
+                scan_case<T>(t, ti, 2, 1, n, p.first, p.second, true, true);
+            }
         }
 }
 

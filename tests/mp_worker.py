@@ -1761,6 +1761,122 @@ def run(pe: int, npes: int, key: str, scenarios: list[str], q, env: dict | None 
             ish.ishmem_free(d_b)
             ish.ishmem_free(s_b)
 
+        if "special" in scenarios:
+            # NaN, infinities, signed zeros, overflow and subnormals (DESIGN.md "Special values"):
+            # oracle.fill_special's table through every form of the host reduce, on whichever path
+            # the environment forces; every result under special_values.compare (NaN where the
+            # team-order fold is NaN, either zero for max / min over zeros of both signs, the
+            # oracle's bits elsewhere).  A one-member team copies bit for bit.
+            from tests import special_values as sv
+            W, INV = ish.ISHMEM_TEAM_WORLD, ish.ISHMEM_TEAM_INVALID
+            GB, PADB, nmax, nbig = 0x3C, 32, 4099, 262_147
+            arena = nmax * 8 + 2 * PADB + 16
+            base_s, base_d = ish.ishmem_malloc(arena), ish.ishmem_malloc(arena)
+            big = ish.ishmem_malloc(nbig * 4)
+            ret = ish.ishmem_malloc(4)
+            st_s = hip.stream_create()
+            r, even = ish.ishmem_team_split_strided(W, 0, 2, (npes + 1) // 2)
+            r1, solo = ish.ishmem_team_split_strided(W, pe, 1, 1)
+            if r or r1 or solo == INV or (even != INV) != (pe % 2 == 0):
+                fails.append(f"pe{pe} special: team splits rc={r}/{r1} even={even} solo={solo} {ish.last_error()}")
+            evens = list(range(0, npes, 2))
+            ran = 0
+
+            def scheck(tag, op, dt, srcs, got):
+                fails.extend(f"pe{pe} special {tag}: {m}" for m in sv.compare(op, dt, srcs, got)[:2])
+
+            def sreduce(tag, op, dt, dst, src, n, team=W, stream=False):
+                """0 if the call succeeded (on a stream: with *ret clean)."""
+                nonlocal ran
+                ran += 1
+                ish.ishmem_barrier_all()  # everyone's source is uploaded, nobody still reads the last one
+                if stream:
+                    hip.memset(ret, 0xFF, 4)
+                    rc = ish.reduce_on_stream(ONAMES[op], NAMES[dt], dst, src, n, ret, st_s, team)
+                    hip.stream_synchronize(st_s)
+                    rc = rc or int(hip.download(ret, 1, np.int32)[0])
+                else:
+                    rc = ish.reduce(ONAMES[op], NAMES[dt], dst, src, n, team)
+                if rc:
+                    fails.append(f"pe{pe} special {tag}: rc={rc} {ish.last_error()}")
+                return rc
+
+            for dt in (DT["float"], DT["double"]):
+                npd = oracle.NP[dt]
+                es = np.dtype(npd).itemsize
+                for op in (OPS["max"], OPS["min"], OPS["sum"], OPS["prod"]):
+                    for n in (5, 1027, nmax):
+                        tag = f"{ONAMES[op]} {NAMES[dt]} n={n}"
+                        srcs = sv.sources(dt, npes, n)
+                        s0, d0 = base_s + PADB, base_d + PADB
+                        hip.upload(s0, srcs[pe])
+                        if not sreduce(tag, op, dt, d0, s0, n):
+                            scheck(tag, op, dt, srcs, hip.download(d0, n, npd))
+                        if not sreduce(tag + " on stream", op, dt, d0, s0, n, stream=True):
+                            scheck(tag + " on stream", op, dt, srcs, hip.download(d0, n, npd))
+                        if not sreduce(tag + " in place", op, dt, s0, s0, n):
+                            scheck(tag + " in place", op, dt, srcs, hip.download(s0, n, npd))
+                        # in place one element off the 16-B grid: head and tail elements
+                        hip.upload(s0 + es, srcs[pe])
+                        if not sreduce(tag + f" in place +{es}", op, dt, s0 + es, s0 + es, n):
+                            scheck(tag + f" in place +{es}", op, dt, srcs, hip.download(s0 + es, n, npd))
+                        # source and dest on different 16-B phases, guard bytes around dest
+                        for so, do in ((es, 0), (0, 16 - es)):
+                            hip.upload(s0 + so, srcs[pe])
+                            hip.memset(base_d, GB, arena)
+                            if sreduce(f"{tag} s+{so} d+{do}", op, dt, d0 + do, s0 + so, n):
+                                continue
+                            raw = hip.download(base_d, arena, np.uint8)
+                            lo, hi = PADB + do, PADB + do + n * es
+                            scheck(f"{tag} s+{so} d+{do}", op, dt, srcs, raw[lo:hi].copy().view(npd))
+                            if not ((raw[:lo] == GB).all() and (raw[hi:] == GB).all()):
+                                fails.append(f"pe{pe} special {tag} s+{so} d+{do}: guard bytes written")
+                        # the strided team of the even PEs (every PE joins the barriers)
+                        tsrcs = sv.sources(dt, len(evens), n)
+                        if even != INV:
+                            hip.upload(s0, tsrcs[evens.index(pe)])
+                        ish.ishmem_barrier_all()
+                        if even != INV:
+                            ran += 1
+                            if ish.reduce(ONAMES[op], NAMES[dt], d0, s0, n, even):
+                                fails.append(f"pe{pe} special {tag} strided team: {ish.last_error()}")
+                            elif len(evens) == 1:
+                                if not _bits_equal(hip.download(d0, n, npd), tsrcs[0]):
+                                    fails.append(f"pe{pe} special {tag} strided team of one: dest != source")
+                            else:
+                                scheck(tag + " strided team", op, dt, tsrcs, hip.download(d0, n, npd))
+                        # a team of one member: a copy, signalling NaNs and payloads included
+                        x = sv.copy_source(dt, n)
+                        hip.upload(s0 + es, x)
+                        hip.memset(base_d, GB, arena)
+                        if not sreduce(tag + " team of one", op, dt, d0, s0 + es, n, team=solo):
+                            raw = hip.download(base_d, arena, np.uint8)
+                            if not np.array_equal(raw[PADB:PADB + n * es], x.view(np.uint8)):
+                                fails.append(f"pe{pe} special {tag} team of one: dest != source bit for bit")
+                            if not ((raw[:PADB] == GB).all() and (raw[PADB + n * es:] == GB).all()):
+                                fails.append(f"pe{pe} special {tag} team of one: guard bytes written")
+                # once from a host buffer, through the staging pipeline
+                op, n = (OPS["sum"], nmax) if dt == DT["float"] else (OPS["max"], 1027)
+                srcs = sv.sources(dt, npes, n)
+                hsrc, hdst = np.ascontiguousarray(srcs[pe]), np.zeros(n, npd)
+                if not sreduce(f"host buffers {ONAMES[op]} {NAMES[dt]}", op, dt, hdst.ctypes.data, hsrc.ctypes.data, n):
+                    scheck(f"host buffers {ONAMES[op]} {NAMES[dt]}", op, dt, srcs, hdst)
+            # in place at 262,147 floats: the size class of the in-place fold through staging
+            srcs = sv.sources(DT["float"], npes, nbig)
+            hip.upload(big, srcs[pe])
+            if not sreduce(f"sum float n={nbig} in place", OPS["sum"], DT["float"], big, big, nbig):
+                scheck(f"sum float n={nbig} in place", OPS["sum"], DT["float"], srcs, hip.download(big, nbig, np.float32))
+            want_calls = 2 * (4 * 3 * 7 + 1) + 1
+            if ran < want_calls and not fails:
+                fails.append(f"pe{pe} special: {ran} of {want_calls} world calls ran")
+            ish.ishmem_barrier_all()
+            hip.stream_destroy(st_s)
+            ish.ishmem_team_destroy(solo)
+            if even != INV:
+                ish.ishmem_team_destroy(even)
+            for b_ in (ret, big, base_d, base_s):
+                ish.ishmem_free(b_)
+
         if ish.lib().ishmemi_c_error_count() != 0:
             fails.append(f"pe{pe} device barrier timeouts: {ish.lib().ishmemi_c_error_count()}")
         ish.ishmem_barrier_all()

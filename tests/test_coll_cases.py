@@ -55,6 +55,36 @@ def test_scan_table_reaches_every_cell_of_every_path(lib, thin):
                     assert (path, vec, inclusive, inplace) in hit, (envname, p, direct, path, vec, inclusive, inplace)
 
 
+def test_special_value_scan_table_reaches_every_cell_of_every_path(lib):
+    # The rows over oracle.fill_special's table (kind "special"): the same cells once more, every
+    # (size, offset pair) of the FP types, and the six-PE teams' float cases both ways.
+    for envname, p, direct, types in runs():
+        ll, fold = live_limits(lib, envname, p, direct)
+        special = cc.special_scan_cases(p, types)
+        assert {c.kind for c in special} == {"special"}
+        assert {c.dtype for c in special} == set(cc.SPECIAL_SCAN_TYPES) & set(types) != set()
+        assert {(c.dtype, c.n, c.so, c.do, c.inplace) for c in special} == {
+            (c.dtype, c.n, c.so, c.do, c.inplace) for c in cc.scan_cases(p, types) if c.dtype in cc.SPECIAL_SCAN_TYPES}
+        hit = set()
+        for c in special:
+            if not direct and c.inplace:
+                continue
+            nb = c.n * cc.SCAN_TYPES[c.dtype]
+            path = cc.scan_path(p, nb, not c.inplace, ll, fold, cc.PHASED_MIN[envname])
+            assert path == cc.scan_target(envname, p, not c.inplace, direct), (envname, p, direct, c, path)
+            hit.add((path, cc.scan_vec(c), c.inclusive, c.inplace))
+        for inplace in ([False] if not direct else [False, True]):
+            path = cc.scan_target(envname, p, not inplace, direct)
+            for vec in (True, False):
+                for inclusive in (True, False):
+                    assert (path, vec, inclusive, inplace) in hit, (envname, p, direct, path, vec, inclusive, inplace)
+    for p in (1, 3, 4, 6):
+        team = cc.special_team_scan_cases(p)
+        assert {c._replace(kind="random") for c in team} == {c for c in cc.team_scan_cases(p) if c.dtype == "float"}
+        assert {c.inclusive for c in team} == {True, False} == {c.inplace for c in team}
+    assert cc.ScanCase("float", True, 1, 0, 0, False).kind == "random"  # the tables' rows as before
+
+
 def test_every_path_is_some_environments_target():
     got = {cc.scan_target(e, p, dj, d) for e, p, d, _ in runs() for dj in (True, False)}
     assert got == {"granule", "direct", "persistent", "phased"}

@@ -295,3 +295,82 @@ def test_realigned_kernels_grid_stride_loop(ish, dt):
         ish.set_param("realign_grid_cap", 0)
         for b in base:
             hip.free(b)
+
+
+# ---- special values: NaN, infinities, signed zeros, overflow, subnormals ------------
+FP_VALID = [(op, dt) for op, dt in VALID if dt >= 8]
+
+
+@pytest.mark.parametrize("op,dt", FP_VALID)
+def test_combine_special_values(ish, op, dt):
+    """The local combine over oracle.fill_special's table, k = 1, 2, 3, 8 sources: aligned (the
+    fan-in kernel) and with every source on another 16-B phase than dest (the realigned kernel from
+    1 KiB), the bytes around dest untouched; every result under special_values.compare (NaN where
+    the team-order fold is NaN, a zero of either sign for max / min over zeros of both signs, the
+    oracle's bits everywhere else)."""
+    from ishmem_amd import hip
+    from tests import special_values as sv
+    es = np.dtype(oracle.NP[dt]).itemsize
+    pad, n_max, k_max = 64, 4099, 8
+    phases = list(range(0, 16, es))
+    base = [hip.malloc(n_max * es + 2 * pad) for _ in range(k_max + 1)]
+    try:
+        for k in (1, 2, 3, 8):
+            for n in (5, 1027, 4099):
+                srcs = sv.sources(dt, k, n)
+                for shift in (0, 1, 2):
+                    # shift 0: all on phase 0; otherwise dest on phase `shift`, source j `j + 1`
+                    # phases further on (never dest's own)
+                    do = phases[shift % len(phases)] if shift else 0
+                    so = [(do + phases[1 + (j + shift) % (len(phases) - 1)]) % 16 if shift else 0 for j in range(k)]
+                    assert not shift or all((s - do) % 16 for s in so)
+                    for j in range(k):
+                        hip.upload(base[j] + pad + so[j], srcs[j])
+                    hip.memset(base[k_max], 0xA5, n_max * es + 2 * pad)
+                    assert ish.combine(ONAMES[op], DNAMES[dt], base[k_max] + pad + do,
+                                       [base[j] + pad + so[j] for j in range(k)], n) == 0, ish.last_error()
+                    hip.synchronize()
+                    raw = hip.download(base[k_max], n_max * es + 2 * pad, np.uint8)
+                    lo, hi = pad + do, pad + do + n * es
+                    got = raw[lo:hi].copy().view(oracle.NP[dt])
+                    assert sv.compare(op, dt, srcs, got) == [], (ONAMES[op], DNAMES[dt], k, n, do, so)
+                    assert (raw[:lo] == 0xA5).all() and (raw[hi:] == 0xA5).all(), (k, n, do, so)
+    finally:
+        for b in base:
+            hip.free(b)
+
+
+@pytest.mark.parametrize("op,dt", FP_VALID)
+def test_single_pe_reduce_copies_special_values_bit_for_bit(ish, op, dt):
+    """One member: dest = source bit for bit, whatever the op — the table's values plus signalling
+    NaNs and NaN payloads (no arithmetic may touch them).  Heap aligned and on a shifted phase, in
+    place, plain device buffers and host buffers."""
+    from ishmem_amd import hip
+    from tests import special_values as sv
+    npd = oracle.NP[dt]
+    es = np.dtype(npd).itemsize
+    pad = 64
+    for n in (5, 1027, 4099):
+        x = sv.copy_source(dt, n)
+        nb = n * es + 2 * pad
+        s_buf, d_buf = ish.ishmem_malloc(nb), ish.ishmem_malloc(nb)
+        for so, do in ((0, 0), (es, 0), (0, 16 - es), (es, es)):
+            hip.upload(s_buf + pad + so, x)
+            hip.memset(d_buf, 0x5A, nb)
+            assert ish.reduce(ONAMES[op], DNAMES[dt], d_buf + pad + do, s_buf + pad + so, n) == 0, ish.last_error()
+            raw = hip.download(d_buf, nb, np.uint8)
+            assert np.array_equal(raw[pad + do: pad + do + n * es], x.view(np.uint8)), (n, so, do)
+            assert (raw[:pad + do] == 0x5A).all() and (raw[pad + do + n * es:] == 0x5A).all(), (n, so, do)
+            assert ish.reduce(ONAMES[op], DNAMES[dt], s_buf + pad + so, s_buf + pad + so, n) == 0  # in place
+            assert _bits_equal(hip.download(s_buf + pad + so, n, npd), x), (n, so, "in place")
+        ds, dd = hip.malloc(nb), hip.malloc(nb)
+        hip.upload(ds + es, x)
+        assert ish.reduce(ONAMES[op], DNAMES[dt], dd, ds + es, n) == 0, ish.last_error()
+        assert _bits_equal(hip.download(dd, n, npd), x), (n, "device buffers")
+        out = np.zeros(n, npd)
+        assert ish.reduce(ONAMES[op], DNAMES[dt], out.ctypes.data, x.ctypes.data, n) == 0, ish.last_error()
+        assert _bits_equal(out, x), (n, "host buffers")
+        for p in (ds, dd):
+            hip.free(p)
+        ish.ishmem_free(d_buf)
+        ish.ishmem_free(s_buf)
