@@ -29,11 +29,12 @@ ENV = {"ISHMEM_MAX_BLOCKS": 32, "ISHMEM_TIMEOUT_MS": 20000, "ISHMEM_SYMMETRIC_SI
        "HSA_ENABLE_IPC_MODE_LEGACY": None}
 
 
-def run_pes(npes: int, scenarios: list[str], timeout: float = 240.0, env: dict | None = None):
+def run_pes(npes: int, scenarios: list[str], timeout: float = 240.0, env: dict | None = None, worker=mp_worker.run):
+    # worker: the per-PE body (tests/staged_worker.py has one with the same arguments).
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     key = f"t{uuid.uuid4().hex[:12]}"
-    procs = [ctx.Process(target=mp_worker.run, args=(pe, npes, key, scenarios, q, {**ENV, **(env or {})}))
+    procs = [ctx.Process(target=worker, args=(pe, npes, key, scenarios, q, {**ENV, **(env or {})}))
              for pe in range(npes)]
     for p in procs:
         p.start()
