@@ -460,6 +460,45 @@ ISHMEMI_CXX_RMA_SIZED(128)
     inline void ishmem_##TYPENAME##_p(TYPE *d, TYPE v, int pe) { ishmem_p(d, v, pe); }              \
     inline TYPE ishmem_##TYPENAME##_g(const TYPE *s, int pe) { return ishmem_g(s, pe); }
 ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_RMA_TYPED, _, _)
+/* ---- strided put / get (src/ishmem.h:122-150, :211-239) ------------------------------------------
+ * ishmem_<TN>_iput / _iget, ishmem_iput<T> / iget<T> and the sized forms: for i < nelems,
+ * dest[i * dst] = source[i * sst]; the strides count elements and are >= 1.  Blocking; the local side
+ * is heap, device or pinned host memory.  The 128-bit forms move 16-byte elements with strides in
+ * 16-byte units.  The blocked forms (ishmemx_ibput / ibget) are in ishmemx.h. */
+template <typename T>
+inline void ishmem_iput(T *dest, const T *source, ptrdiff_t dst, ptrdiff_t sst, size_t nelems, int pe)
+{
+    (void) ishmemi_c_ibput((void *) dest, (const void *) source, dst, sst, 1, nelems, sizeof(T), pe);
+}
+template <typename T>
+inline void ishmem_iget(T *dest, const T *source, ptrdiff_t dst, ptrdiff_t sst, size_t nelems, int pe)
+{
+    (void) ishmemi_c_ibget((void *) dest, (const void *) source, dst, sst, 1, nelems, sizeof(T), pe);
+}
+#define ISHMEMI_CXX_STRIDED_SIZED(BITS)                                                             \
+    inline void ishmem_iput##BITS(void *d, const void *s, ptrdiff_t dst, ptrdiff_t sst, size_t n, int pe) \
+    {                                                                                              \
+        (void) ishmemi_c_ibput(d, s, dst, sst, 1, n, BITS / 8, pe);                                \
+    }                                                                                              \
+    inline void ishmem_iget##BITS(void *d, const void *s, ptrdiff_t dst, ptrdiff_t sst, size_t n, int pe) \
+    {                                                                                              \
+        (void) ishmemi_c_ibget(d, s, dst, sst, 1, n, BITS / 8, pe);                                \
+    }
+ISHMEMI_CXX_STRIDED_SIZED(8)
+ISHMEMI_CXX_STRIDED_SIZED(16)
+ISHMEMI_CXX_STRIDED_SIZED(32)
+ISHMEMI_CXX_STRIDED_SIZED(64)
+ISHMEMI_CXX_STRIDED_SIZED(128)
+#define ISHMEMI_CXX_STRIDED_TYPED(TYPENAME, TYPE, UNUSED1, UNUSED2)                                 \
+    inline void ishmem_##TYPENAME##_iput(TYPE *d, const TYPE *s, ptrdiff_t dst, ptrdiff_t sst, size_t n, int pe) \
+    {                                                                                              \
+        ishmem_iput(d, s, dst, sst, n, pe);                                                        \
+    }                                                                                              \
+    inline void ishmem_##TYPENAME##_iget(TYPE *d, const TYPE *s, ptrdiff_t dst, ptrdiff_t sst, size_t n, int pe) \
+    {                                                                                              \
+        ishmem_iget(d, s, dst, sst, n, pe);                                                        \
+    }
+ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_STRIDED_TYPED, _, _)
 /* ishmem_quiet: every _nbi put / get issued so far by this PE is complete.  ishmem_fence: nothing to
  * do on the host beyond validity (the _nbi stream is in order). */
 inline void ishmem_quiet(void) { (void) ishmemi_c_quiet(); }

@@ -272,6 +272,31 @@ int ishmemi_c_get_on_stream(void *dest, const void *source, size_t nbytes, int p
 int ishmemi_c_quiet(void);
 int ishmemi_c_fence(void);
 int ishmemi_c_quiet_on_stream(void *stream);
+/* ---- strided / blocked put / get — ishmem_<TN>_iput / _iget (src/ishmem.h:122-150, :211-239),
+ *      ishmemx_<TN>_ibput / _ibget and the _on_queue forms (src/ishmemx.h:106-480, src/rma.cpp:125-960) --
+ * For b < nblocks: `bsize` elements of `elem_bytes` bytes (1, 2, 4, 8 or 16) from source + b * sst to
+ * dest + b * dst; the strides count elements, are >= 1 and >= bsize.  iput / iget are bsize == 1.  The
+ * REMOTE side (dest of a put, source of a get) is this PE's symmetric address and lies inside the heap
+ * for its whole extent, ((nblocks - 1) * stride + bsize) * elem_bytes; the local side is heap, device
+ * or pinned host memory (pageable host memory is refused by every strided form).  `pe` in [0, npes);
+ * pe == my_pe is a local strided copy.  nblocks == 0 or bsize == 0 succeeds and launches nothing.
+ * Completion and visibility as put / get (blocking, or ordered by `stream`; capturable); there are no
+ * _nbi strided forms.  Argument errors return nonzero before anything is launched.  One launch
+ * whatever the shape; a transfer that is one contiguous run takes the put / get kernel.
+ * ishmemi_c_strided_plan (pure, no initialised library needed): the layout such a transfer gets.
+ * *item_bytes = the largest power of two <= 16 dividing both addresses, the block's byte length and,
+ * when nblocks > 1, both byte strides; *items_per_block = block bytes / item; *contiguous = 1 when
+ * nblocks <= 1 or both strides equal bsize.  elem_bytes: any value >= 1. */
+int ishmemi_c_ibput(void *dest, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, size_t nblocks,
+                    size_t elem_bytes, int pe);
+int ishmemi_c_ibget(void *dest, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, size_t nblocks,
+                    size_t elem_bytes, int pe);
+int ishmemi_c_ibput_on_stream(void *dest, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, size_t nblocks,
+                              size_t elem_bytes, int pe, void *stream);
+int ishmemi_c_ibget_on_stream(void *dest, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, size_t nblocks,
+                              size_t elem_bytes, int pe, void *stream);
+int ishmemi_c_strided_plan(const void *dest, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, size_t nblocks,
+                           size_t elem_bytes, int *item_bytes, size_t *items_per_block, int *contiguous);
 /* Test hook (no reference counterpart): `grid` workgroups (<= 1024) that EACH read all n uint32 of p
  * with ordinary loads and write their own copy, out[b * n + i] = p[i] (out: grid * n words) — a
  * user's consumer kernel.  Before a peer's put it warms the caches of every CU it ran on with p's

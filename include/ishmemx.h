@@ -435,6 +435,166 @@ ISHMEMI_CXX_RMA_ON_STREAM_T(get_nbi, ishmemi_c_get_on_stream)
     ISHMEMI_CXX_RMA_ON_STREAM_TYPED_ONE(TYPENAME, TYPE, put_nbi)                                    \
     ISHMEMI_CXX_RMA_ON_STREAM_TYPED_ONE(TYPENAME, TYPE, get_nbi)
 ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_RMA_ON_STREAM_TYPED, _, _)
+/* Blocked put / get (ishmemx_<TN>_ibput / _ibget, src/ishmemx.h:170-197, :389-416): for b < nblocks,
+ * `bsize` elements from source + b * sst to dest + b * dst; element strides, >= 1 and >= bsize.
+ * Blocking; and the strided / blocked forms on a stream (ishmemx_*_{iput,iget,ibput,ibget}_on_queue,
+ * src/ishmemx.h:106-480) with the trailing arguments of ishmemx_<TN>_put_on_stream.  The 128-bit forms
+ * count 16-byte elements and 16-byte strides. */
+template <typename T>
+inline void ishmemx_ibput(T *dest, const T *source, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, size_t nblocks, int pe)
+{
+    (void) ishmemi_c_ibput((void *) dest, (const void *) source, dst, sst, bsize, nblocks, sizeof(T), pe);
+}
+template <typename T>
+inline void ishmemx_ibget(T *dest, const T *source, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, size_t nblocks, int pe)
+{
+    (void) ishmemi_c_ibget((void *) dest, (const void *) source, dst, sst, bsize, nblocks, sizeof(T), pe);
+}
+/* NAME: iput / iget (CALL with bsize 1) or ibput / ibget; ARGS / PASS: the count arguments. */
+#define ISHMEMI_CXX_STRIDED_ON_STREAM_T(NAME, CALL, ARGS, PASS)                                     \
+    template <typename T>                                                                          \
+    inline int ishmemx_##NAME##_on_stream(T *dest, const T *source, ptrdiff_t dst, ptrdiff_t sst, ARGS, int pe, \
+                                          hipStream_t stream)                                      \
+    {                                                                                              \
+        return CALL((void *) dest, (const void *) source, dst, sst, PASS, sizeof(T), pe, (void *) stream); \
+    }                                                                                              \
+    template <typename T>                                                                          \
+    inline int ishmemx_##NAME##_on_stream(T *dest, const T *source, ptrdiff_t dst, ptrdiff_t sst, ARGS, int pe, \
+                                          hipStream_t stream, const hipEvent_t *deps, size_t ndeps, hipEvent_t done) \
+    {                                                                                              \
+        return ishmemi_cxx::with_events(stream, deps, ndeps, done, [&] {                           \
+            return CALL((void *) dest, (const void *) source, dst, sst, PASS, sizeof(T), pe, (void *) stream); \
+        });                                                                                        \
+    }
+#define ISHMEMI_CXX_COMMA ,
+ISHMEMI_CXX_STRIDED_ON_STREAM_T(iput, ishmemi_c_ibput_on_stream, size_t nelems, 1 ISHMEMI_CXX_COMMA nelems)
+ISHMEMI_CXX_STRIDED_ON_STREAM_T(iget, ishmemi_c_ibget_on_stream, size_t nelems, 1 ISHMEMI_CXX_COMMA nelems)
+ISHMEMI_CXX_STRIDED_ON_STREAM_T(ibput, ishmemi_c_ibput_on_stream, size_t bsize ISHMEMI_CXX_COMMA size_t nblocks,
+                                bsize ISHMEMI_CXX_COMMA nblocks)
+ISHMEMI_CXX_STRIDED_ON_STREAM_T(ibget, ishmemi_c_ibget_on_stream, size_t bsize ISHMEMI_CXX_COMMA size_t nblocks,
+                                bsize ISHMEMI_CXX_COMMA nblocks)
+#define ISHMEMI_CXX_STRIDED_SIZED_X(BITS)                                                           \
+    inline void ishmemx_ibput##BITS(void *d, const void *s, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, size_t nblocks, \
+                                    int pe)                                                        \
+    {                                                                                              \
+        (void) ishmemi_c_ibput(d, s, dst, sst, bsize, nblocks, BITS / 8, pe);                      \
+    }                                                                                              \
+    inline void ishmemx_ibget##BITS(void *d, const void *s, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, size_t nblocks, \
+                                    int pe)                                                        \
+    {                                                                                              \
+        (void) ishmemi_c_ibget(d, s, dst, sst, bsize, nblocks, BITS / 8, pe);                      \
+    }                                                                                              \
+    inline int ishmemx_iput##BITS##_on_stream(void *d, const void *s, ptrdiff_t dst, ptrdiff_t sst, size_t n, int pe, \
+                                              hipStream_t st)                                      \
+    {                                                                                              \
+        return ishmemi_c_ibput_on_stream(d, s, dst, sst, 1, n, BITS / 8, pe, (void *) st);         \
+    }                                                                                              \
+    inline int ishmemx_iget##BITS##_on_stream(void *d, const void *s, ptrdiff_t dst, ptrdiff_t sst, size_t n, int pe, \
+                                              hipStream_t st)                                      \
+    {                                                                                              \
+        return ishmemi_c_ibget_on_stream(d, s, dst, sst, 1, n, BITS / 8, pe, (void *) st);         \
+    }                                                                                              \
+    inline int ishmemx_ibput##BITS##_on_stream(void *d, const void *s, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, \
+                                               size_t nblocks, int pe, hipStream_t st)             \
+    {                                                                                              \
+        return ishmemi_c_ibput_on_stream(d, s, dst, sst, bsize, nblocks, BITS / 8, pe, (void *) st); \
+    }                                                                                              \
+    inline int ishmemx_ibget##BITS##_on_stream(void *d, const void *s, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, \
+                                               size_t nblocks, int pe, hipStream_t st)             \
+    {                                                                                              \
+        return ishmemi_c_ibget_on_stream(d, s, dst, sst, bsize, nblocks, BITS / 8, pe, (void *) st); \
+    }                                                                                              \
+    inline int ishmemx_iput##BITS##_on_stream(void *d, const void *s, ptrdiff_t dst, ptrdiff_t sst, size_t n, int pe, \
+                                              hipStream_t st, const hipEvent_t *deps, size_t ndeps, hipEvent_t done) \
+    {                                                                                              \
+        return ishmemi_cxx::with_events(st, deps, ndeps, done, [&] {                               \
+            return ishmemi_c_ibput_on_stream(d, s, dst, sst, 1, n, BITS / 8, pe, (void *) st);     \
+        });                                                                                        \
+    }                                                                                              \
+    inline int ishmemx_iget##BITS##_on_stream(void *d, const void *s, ptrdiff_t dst, ptrdiff_t sst, size_t n, int pe, \
+                                              hipStream_t st, const hipEvent_t *deps, size_t ndeps, hipEvent_t done) \
+    {                                                                                              \
+        return ishmemi_cxx::with_events(st, deps, ndeps, done, [&] {                               \
+            return ishmemi_c_ibget_on_stream(d, s, dst, sst, 1, n, BITS / 8, pe, (void *) st);     \
+        });                                                                                        \
+    }                                                                                              \
+    inline int ishmemx_ibput##BITS##_on_stream(void *d, const void *s, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, \
+                                               size_t nblocks, int pe, hipStream_t st, const hipEvent_t *deps, \
+                                               size_t ndeps, hipEvent_t done)                      \
+    {                                                                                              \
+        return ishmemi_cxx::with_events(st, deps, ndeps, done, [&] {                               \
+            return ishmemi_c_ibput_on_stream(d, s, dst, sst, bsize, nblocks, BITS / 8, pe, (void *) st); \
+        });                                                                                        \
+    }                                                                                              \
+    inline int ishmemx_ibget##BITS##_on_stream(void *d, const void *s, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, \
+                                               size_t nblocks, int pe, hipStream_t st, const hipEvent_t *deps, \
+                                               size_t ndeps, hipEvent_t done)                      \
+    {                                                                                              \
+        return ishmemi_cxx::with_events(st, deps, ndeps, done, [&] {                               \
+            return ishmemi_c_ibget_on_stream(d, s, dst, sst, bsize, nblocks, BITS / 8, pe, (void *) st); \
+        });                                                                                        \
+    }
+ISHMEMI_CXX_STRIDED_SIZED_X(8)
+ISHMEMI_CXX_STRIDED_SIZED_X(16)
+ISHMEMI_CXX_STRIDED_SIZED_X(32)
+ISHMEMI_CXX_STRIDED_SIZED_X(64)
+ISHMEMI_CXX_STRIDED_SIZED_X(128)
+#define ISHMEMI_CXX_STRIDED_TYPED_X(TYPENAME, TYPE, UNUSED1, UNUSED2)                               \
+    inline void ishmemx_##TYPENAME##_ibput(TYPE *d, const TYPE *s, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, \
+                                           size_t nblocks, int pe)                                 \
+    {                                                                                              \
+        ishmemx_ibput<TYPE>(d, s, dst, sst, bsize, nblocks, pe);                                   \
+    }                                                                                              \
+    inline void ishmemx_##TYPENAME##_ibget(TYPE *d, const TYPE *s, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, \
+                                           size_t nblocks, int pe)                                 \
+    {                                                                                              \
+        ishmemx_ibget<TYPE>(d, s, dst, sst, bsize, nblocks, pe);                                   \
+    }                                                                                              \
+    inline int ishmemx_##TYPENAME##_iput_on_stream(TYPE *d, const TYPE *s, ptrdiff_t dst, ptrdiff_t sst, size_t n, \
+                                                   int pe, hipStream_t st)                         \
+    {                                                                                              \
+        return ishmemx_iput_on_stream<TYPE>(d, s, dst, sst, n, pe, st);                            \
+    }                                                                                              \
+    inline int ishmemx_##TYPENAME##_iget_on_stream(TYPE *d, const TYPE *s, ptrdiff_t dst, ptrdiff_t sst, size_t n, \
+                                                   int pe, hipStream_t st)                         \
+    {                                                                                              \
+        return ishmemx_iget_on_stream<TYPE>(d, s, dst, sst, n, pe, st);                            \
+    }                                                                                              \
+    inline int ishmemx_##TYPENAME##_ibput_on_stream(TYPE *d, const TYPE *s, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, \
+                                                    size_t nblocks, int pe, hipStream_t st)        \
+    {                                                                                              \
+        return ishmemx_ibput_on_stream<TYPE>(d, s, dst, sst, bsize, nblocks, pe, st);              \
+    }                                                                                              \
+    inline int ishmemx_##TYPENAME##_ibget_on_stream(TYPE *d, const TYPE *s, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, \
+                                                    size_t nblocks, int pe, hipStream_t st)        \
+    {                                                                                              \
+        return ishmemx_ibget_on_stream<TYPE>(d, s, dst, sst, bsize, nblocks, pe, st);              \
+    }                                                                                              \
+    inline int ishmemx_##TYPENAME##_iput_on_stream(TYPE *d, const TYPE *s, ptrdiff_t dst, ptrdiff_t sst, size_t n, \
+                                                   int pe, hipStream_t st, const hipEvent_t *deps, size_t ndeps, \
+                                                   hipEvent_t done)                                \
+    {                                                                                              \
+        return ishmemx_iput_on_stream<TYPE>(d, s, dst, sst, n, pe, st, deps, ndeps, done);         \
+    }                                                                                              \
+    inline int ishmemx_##TYPENAME##_iget_on_stream(TYPE *d, const TYPE *s, ptrdiff_t dst, ptrdiff_t sst, size_t n, \
+                                                   int pe, hipStream_t st, const hipEvent_t *deps, size_t ndeps, \
+                                                   hipEvent_t done)                                \
+    {                                                                                              \
+        return ishmemx_iget_on_stream<TYPE>(d, s, dst, sst, n, pe, st, deps, ndeps, done);         \
+    }                                                                                              \
+    inline int ishmemx_##TYPENAME##_ibput_on_stream(TYPE *d, const TYPE *s, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, \
+                                                    size_t nblocks, int pe, hipStream_t st, const hipEvent_t *deps, \
+                                                    size_t ndeps, hipEvent_t done)                 \
+    {                                                                                              \
+        return ishmemx_ibput_on_stream<TYPE>(d, s, dst, sst, bsize, nblocks, pe, st, deps, ndeps, done); \
+    }                                                                                              \
+    inline int ishmemx_##TYPENAME##_ibget_on_stream(TYPE *d, const TYPE *s, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, \
+                                                    size_t nblocks, int pe, hipStream_t st, const hipEvent_t *deps, \
+                                                    size_t ndeps, hipEvent_t done)                 \
+    {                                                                                              \
+        return ishmemx_ibget_on_stream<TYPE>(d, s, dst, sst, bsize, nblocks, pe, st, deps, ndeps, done); \
+    }
+ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_STRIDED_TYPED_X, _, _)
 inline int ishmemx_quiet_on_stream(hipStream_t stream) { return ishmemi_c_quiet_on_stream((void *) stream); }
 inline int ishmemx_quiet_on_stream(hipStream_t stream, const hipEvent_t *deps, size_t ndeps, hipEvent_t done)
 {

@@ -649,6 +649,119 @@ __device__ inline void rma_call(void *dest, const void *source, size_t nbytes, i
     G::sync();
 }
 
+// ---- strided / blocked put / get from inside a kernel (src/ishmem/copy.h:184-219, :389-427) -----
+// nblocks blocks of bsize elements of ES bytes, block b from src + b * sst to dst + b * dst_stride
+// (element strides), spread over the group.  The item is the host kernel's: the
+// largest power of two <= 16 dividing both addresses, the block's byte length and, for more than one
+// block, both byte strides, so every access is naturally aligned.  Consecutive threads take
+// consecutive items of a block, then the next block's.  Every address is a per-thread 64-bit pointer
+// (base + b * stride + w * W in 64 bits): nothing to wrap however far the extent reaches.
+//   PUT: plain local loads, remote stores system-coherent write-through (sc0 sc1);
+//   GET: remote loads system-coherent (sc0 sc1), plain local stores.
+template <int W>
+struct strided_item {
+    using type = std::conditional_t<W == 8, uint64_t, std::conditional_t<W == 4, uint32_t,
+                 std::conditional_t<W == 2, uint16_t, uint8_t>>>;
+};
+template <>
+struct strided_item<16> {
+    typedef unsigned type __attribute__((ext_vector_type(4)));
+};
+
+template <typename I>
+__device__ __forceinline__ I sys_item_load(const char *p)
+{
+    if constexpr (sizeof(I) == 16) return __builtin_amdgcn_global_load_b128((__attribute__((address_space(1))) I *) p, "");
+    else return sys_load((const I *) p);
+}
+
+template <typename I>
+__device__ __forceinline__ void sys_item_store(char *p, const I &v)
+{
+    if constexpr (sizeof(I) == 16) __builtin_amdgcn_global_store_b128((__attribute__((address_space(1))) I *) p, v, "");
+    else sys_store((I *) p, v);
+}
+
+template <typename G, bool PUT, int W>
+__device__ inline void rma_strided_items(char *dst, const char *src, uint64_t dstride, uint64_t sstride, uint64_t ipb,
+                                         uint64_t nblocks)
+{
+    using I = typename strided_item<W>::type;
+    const uint64_t nthr = (uint64_t) G::size(), nitems = nblocks * ipb;
+    // One division per thread per call; then step nthr items at a time.
+    const uint64_t step_b = nthr / ipb, step_w = nthr - step_b * ipb;
+    uint64_t b = (uint64_t) G::rank() / ipb, w = (uint64_t) G::rank() - b * ipb;
+    for (uint64_t g0 = (uint64_t) G::rank(); g0 < nitems; g0 += nthr * kUnroll) {
+        I x[kUnroll];
+        char *dp[kUnroll];
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            // Threads past the end load item 0 again (and store nothing): no branch round a load, so all
+            // kUnroll loads are in flight before the first store.
+            const char *sp = g0 + (uint64_t) u * nthr < nitems ? src + b * sstride + w * W : src;
+            dp[u] = dst + b * dstride + w * W;
+            if constexpr (PUT) x[u] = *(const I *) sp;
+            else x[u] = sys_item_load<I>(sp);
+            b += step_b;
+            w += step_w;
+            if (w >= ipb) {
+                w -= ipb;
+                ++b;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            if (g0 + (uint64_t) u * nthr >= nitems) continue;
+            if constexpr (PUT) sys_item_store<I>(dp[u], x[u]);
+            else *(I *) dp[u] = x[u];
+        }
+    }
+}
+
+// Not inlined: the five item widths are compiled once per group kind and direction, not once per
+// call site of the few hundred names below.
+template <typename G, bool PUT>
+__device__ __attribute__((noinline)) void rma_strided_group(char *dst, const char *src, uint64_t dstride, uint64_t sstride, uint64_t block_bytes,
+                                         uint64_t nblocks)
+{
+    uint64_t bits = (uint64_t) dst | (uint64_t) src | block_bytes | 16;
+    if (nblocks > 1) bits |= dstride | sstride;
+    const uint64_t wd = bits & (~bits + 1), ipb = block_bytes / wd;
+    switch (wd) {
+        case 16: rma_strided_items<G, PUT, 16>(dst, src, dstride, sstride, ipb, nblocks); break;
+        case 8: rma_strided_items<G, PUT, 8>(dst, src, dstride, sstride, ipb, nblocks); break;
+        case 4: rma_strided_items<G, PUT, 4>(dst, src, dstride, sstride, ipb, nblocks); break;
+        case 2: rma_strided_items<G, PUT, 2>(dst, src, dstride, sstride, ipb, nblocks); break;
+        default: rma_strided_items<G, PUT, 1>(dst, src, dstride, sstride, ipb, nblocks); break;
+    }
+}
+
+// Blocking strided / blocked put / get by the group G: the sync, drain, sync bracket of rma_call.
+// Strides < 1 or < bsize are an argument error (device error word, nothing moved).
+template <typename G, bool PUT>
+__device__ inline void rma_strided_call(void *dest, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t bsize,
+                                        size_t nblocks, size_t elem_bytes, int pe)
+{
+    const ishmemi_c_device_ctx_t *c = ctx();
+    if (!c || pe < 0 || pe >= c->npes) return;
+    if (dst < 1 || sst < 1 || (size_t) dst < bsize || (size_t) sst < bsize) {
+        if (G::rank() == 0)  // kErrBadArgument
+            __hip_atomic_fetch_or(c->err, 1u << 9, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        return;
+    }
+    G::sync();
+    if (nblocks && bsize) {
+        if constexpr (PUT)
+            rma_strided_group<G, true>(peer_addr(c, dest, pe), (const char *) source, (uint64_t) dst * elem_bytes,
+                                       (uint64_t) sst * elem_bytes, (uint64_t) bsize * elem_bytes, nblocks);
+        else
+            rma_strided_group<G, false>((char *) dest, peer_addr(c, source, pe), (uint64_t) dst * elem_bytes,
+                                        (uint64_t) sst * elem_bytes, (uint64_t) bsize * elem_bytes, nblocks);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    G::sync();
+}
+
 // quiet / fence: the calling thread's outstanding memory operations, then a system-scope release
 // (the second wait is kept: the fence's own may be dropped by the compiler).
 template <typename G>
@@ -1261,6 +1374,102 @@ __device__ inline T ishmem_g(const T *source, int pe)
     __device__ inline void ishmem_##TYPENAME##_p(TYPE *d, TYPE v, int pe) { ishmem_p<TYPE>(d, v, pe); } \
     __device__ inline TYPE ishmem_##TYPENAME##_g(const TYPE *s, int pe) { return ishmem_g<TYPE>(s, pe); }
 ISHMEMX_DEV_ARITH_TYPES(ISHMEMX_DEV_RMA_TYPED, _, _)
+/* Strided / blocked put / get from a kernel (src/ishmem.h:122-150, :211-239, src/ishmemx.h:137-480):
+ * ishmem_<TN>_iput / _iget and ishmemx_<TN>_ibput / _ibget (one work-item, its own arguments),
+ * ishmemx_<TN>_iput_work_group / _iget_work_group / _ibput_work_group / _ibget_work_group (every thread
+ * of the group, same arguments), the generic templates and the sized forms (8..128; the 128-bit forms
+ * count 16-byte elements and strides).  Element strides, >= 1 and >= bsize. */
+#define ISHMEMX_DEV_STRIDED_GENERIC(DIR, PUT)                                                       \
+    template <typename T>                                                                          \
+    __device__ inline void ishmem_i##DIR(T *dest, const T *source, ptrdiff_t dst, ptrdiff_t sst, size_t nelems, int pe) \
+    {                                                                                              \
+        ishmemx_dev::rma_strided_call<ishmemx_dev::thread_t, PUT>((void *) dest, (const void *) source, dst, sst, 1, \
+                                                                  nelems, sizeof(T), pe);          \
+    }                                                                                              \
+    template <typename T, typename Group>                                                          \
+    __device__ inline void ishmemx_i##DIR##_work_group(T *dest, const T *source, ptrdiff_t dst, ptrdiff_t sst, \
+                                                       size_t nelems, int pe, const Group &)       \
+    {                                                                                              \
+        ishmemx_dev::rma_strided_call<ishmemx_dev::exec_t<Group>, PUT>((void *) dest, (const void *) source, dst, sst, \
+                                                                       1, nelems, sizeof(T), pe);  \
+    }                                                                                              \
+    template <typename T>                                                                          \
+    __device__ inline void ishmemx_ib##DIR(T *dest, const T *source, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, \
+                                           size_t nblocks, int pe)                                 \
+    {                                                                                              \
+        ishmemx_dev::rma_strided_call<ishmemx_dev::thread_t, PUT>((void *) dest, (const void *) source, dst, sst, \
+                                                                  bsize, nblocks, sizeof(T), pe);  \
+    }                                                                                              \
+    template <typename T, typename Group>                                                          \
+    __device__ inline void ishmemx_ib##DIR##_work_group(T *dest, const T *source, ptrdiff_t dst, ptrdiff_t sst, \
+                                                        size_t bsize, size_t nblocks, int pe, const Group &) \
+    {                                                                                              \
+        ishmemx_dev::rma_strided_call<ishmemx_dev::exec_t<Group>, PUT>((void *) dest, (const void *) source, dst, sst, \
+                                                                       bsize, nblocks, sizeof(T), pe); \
+    }
+ISHMEMX_DEV_STRIDED_GENERIC(put, true)
+ISHMEMX_DEV_STRIDED_GENERIC(get, false)
+#define ISHMEMX_DEV_STRIDED_SIZED(DIR, PUT, BITS)                                                   \
+    __device__ inline void ishmem_i##DIR##BITS(void *dest, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t n, \
+                                               int pe)                                             \
+    {                                                                                              \
+        ishmemx_dev::rma_strided_call<ishmemx_dev::thread_t, PUT>(dest, source, dst, sst, 1, n, BITS / 8, pe); \
+    }                                                                                              \
+    template <typename Group>                                                                      \
+    __device__ inline void ishmemx_i##DIR##BITS##_work_group(void *dest, const void *source, ptrdiff_t dst, \
+                                                             ptrdiff_t sst, size_t n, int pe, const Group &) \
+    {                                                                                              \
+        ishmemx_dev::rma_strided_call<ishmemx_dev::exec_t<Group>, PUT>(dest, source, dst, sst, 1, n, BITS / 8, pe); \
+    }                                                                                              \
+    __device__ inline void ishmemx_ib##DIR##BITS(void *dest, const void *source, ptrdiff_t dst, ptrdiff_t sst, \
+                                                 size_t bsize, size_t nblocks, int pe)             \
+    {                                                                                              \
+        ishmemx_dev::rma_strided_call<ishmemx_dev::thread_t, PUT>(dest, source, dst, sst, bsize, nblocks, BITS / 8, pe); \
+    }                                                                                              \
+    template <typename Group>                                                                      \
+    __device__ inline void ishmemx_ib##DIR##BITS##_work_group(void *dest, const void *source, ptrdiff_t dst, \
+                                                              ptrdiff_t sst, size_t bsize, size_t nblocks, int pe, \
+                                                              const Group &)                       \
+    {                                                                                              \
+        ishmemx_dev::rma_strided_call<ishmemx_dev::exec_t<Group>, PUT>(dest, source, dst, sst, bsize, nblocks, \
+                                                                       BITS / 8, pe);              \
+    }
+#define ISHMEMX_DEV_STRIDED_SIZED_BOTH(BITS)                                                        \
+    ISHMEMX_DEV_STRIDED_SIZED(put, true, BITS)                                                      \
+    ISHMEMX_DEV_STRIDED_SIZED(get, false, BITS)
+ISHMEMX_DEV_STRIDED_SIZED_BOTH(8)
+ISHMEMX_DEV_STRIDED_SIZED_BOTH(16)
+ISHMEMX_DEV_STRIDED_SIZED_BOTH(32)
+ISHMEMX_DEV_STRIDED_SIZED_BOTH(64)
+ISHMEMX_DEV_STRIDED_SIZED_BOTH(128)
+#define ISHMEMX_DEV_STRIDED_TYPED_ONE(TYPENAME, TYPE, DIR)                                          \
+    __device__ inline void ishmem_##TYPENAME##_i##DIR(TYPE *d, const TYPE *s, ptrdiff_t dst, ptrdiff_t sst, size_t n, \
+                                                      int pe)                                      \
+    {                                                                                              \
+        ishmem_i##DIR<TYPE>(d, s, dst, sst, n, pe);                                                \
+    }                                                                                              \
+    template <typename Group>                                                                      \
+    __device__ inline void ishmemx_##TYPENAME##_i##DIR##_work_group(TYPE *d, const TYPE *s, ptrdiff_t dst, \
+                                                                    ptrdiff_t sst, size_t n, int pe, const Group &grp) \
+    {                                                                                              \
+        ishmemx_i##DIR##_work_group<TYPE>(d, s, dst, sst, n, pe, grp);                             \
+    }                                                                                              \
+    __device__ inline void ishmemx_##TYPENAME##_ib##DIR(TYPE *d, const TYPE *s, ptrdiff_t dst, ptrdiff_t sst, \
+                                                        size_t bsize, size_t nblocks, int pe)      \
+    {                                                                                              \
+        ishmemx_ib##DIR<TYPE>(d, s, dst, sst, bsize, nblocks, pe);                                 \
+    }                                                                                              \
+    template <typename Group>                                                                      \
+    __device__ inline void ishmemx_##TYPENAME##_ib##DIR##_work_group(TYPE *d, const TYPE *s, ptrdiff_t dst, \
+                                                                     ptrdiff_t sst, size_t bsize, size_t nblocks, \
+                                                                     int pe, const Group &grp)     \
+    {                                                                                              \
+        ishmemx_ib##DIR##_work_group<TYPE>(d, s, dst, sst, bsize, nblocks, pe, grp);               \
+    }
+#define ISHMEMX_DEV_STRIDED_TYPED(TYPENAME, TYPE, UNUSED1, UNUSED2)                                 \
+    ISHMEMX_DEV_STRIDED_TYPED_ONE(TYPENAME, TYPE, put)                                              \
+    ISHMEMX_DEV_STRIDED_TYPED_ONE(TYPENAME, TYPE, get)
+ISHMEMX_DEV_ARITH_TYPES(ISHMEMX_DEV_STRIDED_TYPED, _, _)
 __device__ inline void ishmem_quiet(void) { ishmemx_dev::quiet_group<ishmemx_dev::thread_t>(); }
 __device__ inline void ishmem_fence(void) { ishmemx_dev::quiet_group<ishmemx_dev::thread_t>(); }
 template <typename Group>

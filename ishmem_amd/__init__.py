@@ -480,6 +480,71 @@ for _bits in (8, 16, 32, 64, 128):  # ishmem_put8 .. ishmem_get128 (elements of 
             RMA_NAMES.append(_name)
 del _tn, _kind, _name, _f, _put, _nbi, _bits
 
+
+# ---- strided / blocked put / get (src/ishmem.h:122-150, :211-239, src/ishmemx.h:106-480) --
+# ishmem_<TN>_iput / _iget(dest, source, dst, sst, nelems, pe) and ishmemx_<TN>_ibput / _ibget(dest,
+# source, dst, sst, bsize, nblocks, pe), the sized forms (the 128-bit ones count 16-byte elements and
+# strides) and the stream-ordered helpers.  Strides count elements.  0 / nonzero like put / get.
+def ibput(dest: int, source: int, dst: int, sst: int, bsize: int, nblocks: int, elem_bytes: int, pe: int) -> int:
+    return _L.ishmemi_c_ibput(dest or None, source or None, dst, sst, bsize, nblocks, elem_bytes, pe)
+
+
+def ibget(dest: int, source: int, dst: int, sst: int, bsize: int, nblocks: int, elem_bytes: int, pe: int) -> int:
+    return _L.ishmemi_c_ibget(dest or None, source or None, dst, sst, bsize, nblocks, elem_bytes, pe)
+
+
+def _strided_on_stream(fn, dest, source, dst, sst, bsize, nblocks, elem_bytes, pe, stream, deps, done) -> int:
+    def call(d, s, n, p, st):
+        return fn(d or None, s or None, dst, sst, bsize, nblocks, elem_bytes, p, st)
+    return _rma_on_stream(call, dest, source, 0, pe, stream, deps, done)
+
+
+def ibput_on_stream(dest: int, source: int, dst: int, sst: int, bsize: int, nblocks: int, elem_bytes: int, pe: int,
+                    stream: int, deps=(), done=None) -> int:
+    """ishmemx_ibput<bits>_on_queue analogue; iput is bsize == 1."""
+    return _strided_on_stream(_L.ishmemi_c_ibput_on_stream, dest, source, dst, sst, bsize, nblocks, elem_bytes, pe, stream,
+                              deps, done)
+
+
+def ibget_on_stream(dest: int, source: int, dst: int, sst: int, bsize: int, nblocks: int, elem_bytes: int, pe: int,
+                    stream: int, deps=(), done=None) -> int:
+    return _strided_on_stream(_L.ishmemi_c_ibget_on_stream, dest, source, dst, sst, bsize, nblocks, elem_bytes, pe, stream,
+                              deps, done)
+
+
+def strided_plan(dest: int, source: int, dst: int, sst: int, bsize: int, nblocks: int, elem_bytes: int) -> tuple[int, int, bool]:
+    """(item bytes, items per block, contiguous) of such a transfer (no initialised library needed)."""
+    w, ipb, cont = ctypes.c_int(0), ctypes.c_size_t(0), ctypes.c_int(0)
+    if _L.ishmemi_c_strided_plan(dest or None, source or None, dst, sst, bsize, nblocks, elem_bytes, ctypes.byref(w),
+                                 ctypes.byref(ipb), ctypes.byref(cont)):
+        raise ValueError(f"strided_plan: {last_error()}")
+    return w.value, ipb.value, bool(cont.value)
+
+
+def _make_strided(put: bool, blocked: bool, size: int):
+    call = ibput if put else ibget
+    if blocked:
+        def fn(dest: int, source: int, dst: int, sst: int, bsize: int, nblocks: int, pe: int) -> int:
+            return call(dest, source, dst, sst, bsize, nblocks, size, pe)
+    else:
+        def fn(dest: int, source: int, dst: int, sst: int, nelems: int, pe: int) -> int:
+            return call(dest, source, dst, sst, 1, nelems, size, pe)
+    return fn
+
+
+STRIDED_NAMES: list[str] = []
+for _put in (True, False):
+    for _blocked in (False, True):
+        _op = ("ib" if _blocked else "i") + ("put" if _put else "get")
+        _prefix = "ishmemx" if _blocked else "ishmem"
+        for _name, _size in [(f"{_prefix}_{_tn}_{_op}", _SIZES[TYPENAMES[_tn]]) for _tn in ARITH_TYPENAMES] + \
+                [(f"{_prefix}_{_op}{_bits}", _bits // 8) for _bits in (8, 16, 32, 64, 128)]:
+            _f = _make_strided(_put, _blocked, _size)
+            _f.__name__ = _name
+            setattr(_mod, _name, _f)
+            STRIDED_NAMES.append(_name)
+del _put, _blocked, _op, _prefix, _name, _size, _f
+
 # ---- put with signal, signal operations, wait_until / test (src/ishmem.h:28-36, :640-705, :1320-1354,
 #      :1551-1552; DESIGN.md §3c) --------------------------------------------------------------------
 # The signal word (a symmetric uint64) is updated on the target only after the payload is in its

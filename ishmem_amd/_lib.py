@@ -16,6 +16,7 @@ _VARIANT = os.environ.get("ISHMEM_AMD_LIB")
 
 # (name, restype, argtypes) for every symbol declared in include/ishmem_capi.h.
 _vp, _i, _sz, _ll, _u64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t, ctypes.c_longlong, ctypes.c_uint64
+_pd = ctypes.c_ssize_t  # ptrdiff_t
 PROTOTYPES = [
     ("ishmemi_c_init", _i, []),
     ("ishmemi_c_init_pe", _i, [_i, _i, _i, ctypes.c_char_p]),
@@ -68,6 +69,12 @@ PROTOTYPES = [
     ("ishmemi_c_quiet", _i, []),
     ("ishmemi_c_fence", _i, []),
     ("ishmemi_c_quiet_on_stream", _i, [_vp]),
+    ("ishmemi_c_ibput", _i, [_vp, _vp, _pd, _pd, _sz, _sz, _sz, _i]),
+    ("ishmemi_c_ibget", _i, [_vp, _vp, _pd, _pd, _sz, _sz, _sz, _i]),
+    ("ishmemi_c_ibput_on_stream", _i, [_vp, _vp, _pd, _pd, _sz, _sz, _sz, _i, _vp]),
+    ("ishmemi_c_ibget_on_stream", _i, [_vp, _vp, _pd, _pd, _sz, _sz, _sz, _i, _vp]),
+    ("ishmemi_c_strided_plan", _i, [_vp, _vp, _pd, _pd, _sz, _sz, _sz, ctypes.POINTER(_i), ctypes.POINTER(_sz),
+                                    ctypes.POINTER(_i)]),
     ("ishmemi_c_read_all_u32", _i, [_vp, _vp, _sz, _i, _vp]),
     ("ishmemi_c_put_signal", _i, [_vp, _vp, _sz, _vp, _u64, _i, _i]),
     ("ishmemi_c_put_signal_nbi", _i, [_vp, _vp, _sz, _vp, _u64, _i, _i]),

@@ -318,6 +318,27 @@ struct RmaArgs {
     uint64_t head, nitems, tail;
 };
 hipError_t launch_rma_copy(const RmaArgs &a, bool put, int max_blocks, hipStream_t s);
+// Strided / blocked put / get (kernels_rma.hip rma_strided_kernel): `nblocks` blocks of
+// `ipb` items of `item` bytes (1, 2, 4, 8 or 16); block b goes from src + b * src_stride to
+// dst + b * dst_stride (byte strides).  `item` divides both addresses, both strides and the block's
+// byte length (strided_plan).  One of dst / src is a peer's heap as mapped in this process; cache
+// policy and grid as launch_rma_copy.
+struct StridedArgs {
+    char *dst;
+    const char *src;
+    uint64_t dst_stride, src_stride;
+    uint64_t nblocks, ipb;
+    uint32_t item;
+};
+hipError_t launch_rma_strided(const StridedArgs &a, bool put, int max_blocks, hipStream_t s);
+// The layout of a strided / blocked transfer of `nblocks` blocks of `bsize` elements of `elem_bytes`
+// bytes with element strides `dst` / `sst` (pure; no library state).  *item_bytes: the largest power of
+// two <= 16 that divides both addresses, the block's byte length and, when nblocks > 1, both byte
+// strides; *items_per_block: block bytes / item; *contiguous: 1 when the transfer is one contiguous
+// copy (nblocks <= 1, or both strides equal to bsize), which goes to the contiguous kernel.  Returns
+// false when a byte count overflows 64 bits or elem_bytes is 0.
+bool strided_plan(const void *dest, const void *source, uint64_t dst, uint64_t sst, uint64_t bsize, uint64_t nblocks,
+                  uint64_t elem_bytes, uint32_t *item_bytes, uint64_t *items_per_block, int *contiguous);
 // Test hook: `grid` workgroups that each read all n words of p with plain loads into out[b * n ..].
 hipError_t launch_read_all_u32(uint32_t *out, const uint32_t *p, uint64_t n, int grid, hipStream_t s);
 

@@ -1665,6 +1665,83 @@ int rma_impl(bool put, void *dest, const void *source, size_t nbytes, int pe, Rm
     return host_wait(s, st);
 }
 
+// ---------------- strided / blocked put / get --------------------------------------
+// ishmem_iput / iget, ishmemx_ibput / ibget (src/rma.cpp:125-960): block b of `bsize` elements goes
+// from source + b * sst to dest + b * dst (element strides); iput / iget are bsize == 1.  One launch of
+// rma_strided_kernel; a transfer that is one contiguous run goes to rma_impl.  Blocking or on a
+// stream (the reference has no _nbi strided forms); the local side must be device-accessible.
+int strided_impl(bool put, void *dest, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, size_t nblocks,
+                 size_t elem_bytes, int pe, RmaKind kind, hipStream_t user)
+{
+    const std::string what = std::string(put ? "ibput" : "ibget") + (kind == kRmaOnStream ? "_on_stream" : "");
+    uint32_t item = 0;
+    uint64_t ipb = 0;
+    int contiguous = 0;
+    {
+        State &s = S();
+        std::lock_guard<std::mutex> lk(s.mu);
+        if (!s.initialized) return fail(what + ": not initialized");
+        if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8 && elem_bytes != 16)
+            return fail(what + ": elem_bytes " + std::to_string(elem_bytes) + " is not 1, 2, 4, 8 or 16");
+        if (pe < 0 || pe >= s.npes)
+            return fail(what + ": pe " + std::to_string(pe) + " outside [0, " + std::to_string(s.npes) + ")");
+        if (dst < 1 || sst < 1)
+            return fail(what + ": stride " + std::to_string(dst < 1 ? dst : sst) + " is not positive (strides are >= 1)");
+        if ((uint64_t) dst < bsize || (uint64_t) sst < bsize)
+            return fail(what + ": stride " + std::to_string((uint64_t) dst < bsize ? dst : sst) + " is less than the block size " +
+                        std::to_string(bsize));
+        if (nblocks == 0 || bsize == 0) return 0;
+        if (!dest || !source) return fail(what + ": null pointer with a nonempty transfer");
+        // Extents in bytes, ((nblocks - 1) * stride + bsize) * elem_bytes, in 64 bits with an overflow check.
+        uint64_t ext[2];
+        for (int k = 0; k < 2; ++k) {
+            uint64_t e = 0;
+            if (__builtin_mul_overflow((uint64_t) (nblocks - 1), (uint64_t) (k ? sst : dst), &e) ||
+                __builtin_add_overflow(e, (uint64_t) bsize, &e) || __builtin_mul_overflow(e, (uint64_t) elem_bytes, &e))
+                return fail(what + (k ? ": source" : ": dest") + " extent overflows 64 bits");
+            ext[k] = e;
+        }
+        uint64_t payload = 0;
+        if (__builtin_mul_overflow((uint64_t) nblocks, (uint64_t) bsize, &payload) ||
+            __builtin_mul_overflow(payload, (uint64_t) elem_bytes, &payload))
+            return fail(what + ": payload overflows 64 bits");
+        const char *sym = put ? (const char *) dest : (const char *) source;
+        if (!in_heap(s, sym) || ext[put ? 0 : 1] > (uint64_t) (s.heap + s.heap_size - sym))
+            return fail(what + (put ? ": dest" : ": source") + " is not inside the symmetric heap for its whole extent");
+        char *remote = translate(s, sym, pe);
+        if (!remote) return fail(what + ": heap of PE " + std::to_string(pe) + " not mapped");
+        const void *lp = put ? source : (const void *) dest;
+        char *local = device_view(s, lp);
+        const uint64_t lext = ext[put ? 1 : 0];
+        if (!local || (uintptr_t) lp + lext < (uintptr_t) lp)
+            return fail(what + (put ? ": source" : ": dest") + " is not device-accessible (heap, device or pinned host "
+                        "memory; the strided forms refuse pageable host memory)");
+        if (!strided_plan(put ? (const void *) remote : (const void *) local, put ? (const void *) local : (const void *) remote,
+                          (uint64_t) dst, (uint64_t) sst, bsize, nblocks, elem_bytes, &item, &ipb, &contiguous))
+            return fail(what + ": byte strides overflow 64 bits");
+        if (!contiguous) {
+            StridedArgs a{};
+            a.dst = put ? remote : local;
+            a.src = put ? local : remote;
+            a.dst_stride = (uint64_t) dst * elem_bytes;
+            a.src_stride = (uint64_t) sst * elem_bytes;
+            a.nblocks = nblocks;
+            a.ipb = ipb;
+            a.item = item;
+            hipStream_t st = 0;
+            if (kind == kRmaOnStream) {
+                st = user;
+                if (order_stream(s, st)) return 1;
+            }
+            HIP_TRY(launch_rma_strided(a, put, s.max_blocks, st));
+            if (kind == kRmaOnStream) return mark_stream(s, st);
+            return host_wait(s, st);
+        }
+    }
+    // One contiguous run of nblocks * bsize elements: the contiguous kernel (it takes the lock itself).
+    return rma_impl(put, dest, source, nblocks * bsize * elem_bytes, pe, kind, user);
+}
+
 // ---------------- put with signal, signal operations, wait_until / test ----------
 // ishmem_put_signal / ishmemx_signal_set / add / ishmem_signal_fetch / ishmem_signal_wait_until /
 // ishmem_<TN>_wait_until / _test (src/signaling.cpp, src/synchronization.cpp).  The payload goes
@@ -2864,6 +2941,25 @@ int resolve_launch(LaunchInfo &li)
 }
 
 }  // namespace
+
+bool strided_plan(const void *dest, const void *source, uint64_t dst, uint64_t sst, uint64_t bsize, uint64_t nblocks,
+                  uint64_t elem_bytes, uint32_t *item_bytes, uint64_t *items_per_block, int *contiguous)
+{
+    uint64_t block = 0, dbytes = 0, sbytes = 0;
+    if (elem_bytes == 0 || __builtin_mul_overflow(bsize, elem_bytes, &block) ||
+        __builtin_mul_overflow(dst, elem_bytes, &dbytes) || __builtin_mul_overflow(sst, elem_bytes, &sbytes))
+        return false;
+    // Every quantity an item's address is built from; the lowest set bit of their OR is the widest
+    // power of two dividing them all.
+    uint64_t bits = (uint64_t) (uintptr_t) dest | (uint64_t) (uintptr_t) source | block | 16;
+    if (nblocks > 1) bits |= dbytes | sbytes;
+    const uint64_t w = bits & (~bits + 1);
+    *item_bytes = (uint32_t) w;
+    *items_per_block = block / w;
+    *contiguous = (nblocks <= 1 || (dst == bsize && sst == bsize)) ? 1 : 0;
+    return true;
+}
+
 }  // namespace ishmemi
 
 using namespace ishmemi;
@@ -3459,6 +3555,44 @@ int ishmemi_c_put_on_stream(void *dest, const void *source, size_t nbytes, int p
 int ishmemi_c_get_on_stream(void *dest, const void *source, size_t nbytes, int pe, void *stream)
 {
     return rma_impl(false, dest, source, nbytes, pe, kRmaOnStream, (hipStream_t) stream);
+}
+
+int ishmemi_c_ibput(void *dest, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, size_t nblocks,
+                    size_t elem_bytes, int pe)
+{
+    return strided_impl(true, dest, source, dst, sst, bsize, nblocks, elem_bytes, pe, kRmaBlocking, 0);
+}
+
+int ishmemi_c_ibget(void *dest, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, size_t nblocks,
+                    size_t elem_bytes, int pe)
+{
+    return strided_impl(false, dest, source, dst, sst, bsize, nblocks, elem_bytes, pe, kRmaBlocking, 0);
+}
+
+int ishmemi_c_ibput_on_stream(void *dest, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, size_t nblocks,
+                              size_t elem_bytes, int pe, void *stream)
+{
+    return strided_impl(true, dest, source, dst, sst, bsize, nblocks, elem_bytes, pe, kRmaOnStream, (hipStream_t) stream);
+}
+
+int ishmemi_c_ibget_on_stream(void *dest, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, size_t nblocks,
+                              size_t elem_bytes, int pe, void *stream)
+{
+    return strided_impl(false, dest, source, dst, sst, bsize, nblocks, elem_bytes, pe, kRmaOnStream, (hipStream_t) stream);
+}
+
+int ishmemi_c_strided_plan(const void *dest, const void *source, ptrdiff_t dst, ptrdiff_t sst, size_t bsize, size_t nblocks,
+                           size_t elem_bytes, int *item_bytes, size_t *items_per_block, int *contiguous)
+{
+    if (!item_bytes || !items_per_block || !contiguous) return fail("strided_plan: null out-pointer");
+    if (dst < 0 || sst < 0) return fail("strided_plan: negative stride");
+    uint32_t w = 0;
+    uint64_t ipb = 0;
+    if (!strided_plan(dest, source, (uint64_t) dst, (uint64_t) sst, bsize, nblocks, elem_bytes, &w, &ipb, contiguous))
+        return fail("strided_plan: elem_bytes is 0 or a byte count overflows 64 bits");
+    *item_bytes = (int) w;
+    *items_per_block = (size_t) ipb;
+    return 0;
 }
 
 int ishmemi_c_quiet(void)
