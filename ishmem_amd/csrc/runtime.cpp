@@ -682,19 +682,77 @@ int check_team_errors(State &s, int team)
     return 0;
 }
 
+bool valid_team(const State &s, int team) { return team >= 0 && team < kMaxTeams && s.teams[team].valid; }
+
+// The caller may run a collective of `team`: the library is up and the caller a member.
+bool member_call(const State &s, int team) { return s.initialized && valid_team(s, team) && s.teams[team].my_idx >= 0; }
+
+// Prologue of the collectives that report exactly these two texts (the others word their own
+// around valid_team / member_call).
+int team_call(const State &s, const char *name, int team)
+{
+    if (!s.initialized) return fail(std::string(name) + ": not initialized");
+    if (!member_call(s, team)) return fail(std::string(name) + ": invalid team or caller not a member");
+    return 0;
+}
+
 enum class Kind { Heap, Device, Host };
 
-Kind classify(const State &s, const void *p)
+// What the runtime knows about a caller's pointer: inside this PE's symmetric heap (then HIP is not
+// asked), else what HIP's pointer-attribute query said.  Every "what kind of memory is this" question of
+// the host entry points is an accessor here, so a call asks HIP once per buffer (ptr_info).
+struct PtrInfo {
+    const void *p = nullptr;
+    bool filled = false, heap = false, ok = false;  // ok: the query succeeded (it fails for plain malloc memory)
+    hipMemoryType type = hipMemoryTypeUnregistered;
+    void *dev = nullptr;  // the device pointer of host memory the GPU can address
+
+    bool device_mem() const { return ok && (type == hipMemoryTypeDevice || type == hipMemoryTypeManaged); }
+    Kind kind() const { return heap ? Kind::Heap : device_mem() ? Kind::Device : Kind::Host; }
+    // Plain malloc memory (not page-locked): the DMA engines cannot address it (CallPins).
+    bool pageable() const { return !heap && (!ok || type == hipMemoryTypeUnregistered || (type == hipMemoryTypeHost && !dev)); }
+    // Device address of host memory the GPU can load / store directly (hipHostMalloc'd, or registered
+    // by the caller or by CallPins), else null.
+    char *host_view() const { return ok && type == hipMemoryTypeHost ? (char *) dev : nullptr; }
+    // The address a kernel of this device uses for the pointer (heap, device, managed or pinned /
+    // registered host memory); null for memory it cannot reach (pageable host memory).
+    char *view() const
+    {
+        if (heap || device_mem()) return (char *) p;
+        return host_view();
+    }
+};
+
+// Fills `i` for `p` unless it already holds the answer, so a value handed down a call is asked once.
+const PtrInfo &ptr_info(const State &s, const void *p, PtrInfo &i)
 {
-    if (in_heap(s, p)) return Kind::Heap;
+    if (i.filled && i.p == p) return i;
+    i = PtrInfo{};
+    i.p = p;
+    i.filled = true;
+    i.heap = in_heap(s, p);
+    if (i.heap) return i;
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, p) == hipSuccess) {
-        if (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged) return Kind::Device;
-        return Kind::Host;
+        i.ok = true;
+        i.type = attr.type;
+        i.dev = attr.devicePointer;
+    } else {
+        (void) hipGetLastError();  // not sticky: the next HIP call must not report this one
     }
-    (void) hipGetLastError();
-    return Kind::Host;
+    return i;
 }
+
+PtrInfo ptr_info(const State &s, const void *p)
+{
+    PtrInfo i;
+    return ptr_info(s, p, i);
+}
+
+Kind classify(const State &s, const void *p) { return ptr_info(s, p).kind(); }
+char *device_view(const State &s, const void *p) { return ptr_info(s, p).view(); }
+// Memory a kernel of this device may write: the heap, device memory, pinned host memory.
+bool device_writable(const State &s, const void *p) { return device_view(s, p) != nullptr; }
 
 // Fan-in operands whose addresses differ mod 16 (no common vector body): with 1 or 2 sources and
 // every operand element-aligned, the realigned kernel (kernels_impl.h fanin_realign_kernel) runs
@@ -882,14 +940,19 @@ int host_wait(State &s, hipStream_t st)
 // phased call, 8 co-located PEs 651-687 vs 130-175 us, two-stream probe 9.6 vs 5.7 us per
 // barrier), had no timeout, and had to fall back to this kernel under stream capture — a path
 // choice one PE could make differently from its peers — so round 6 removed it.
-int team_barrier(State &s, int team, const ReduceArgs &a, hipStream_t st)
+int team_barrier(const ReduceArgs &a, hipStream_t st)
 {
-    (void) s;
-    (void) team;
     HIP_TRY(launch_team_sync(a, st));
     return 0;
 }
 
+// The barrier's arguments: the team's, with the call's sticky *ret.
+int barrier_args(State &s, int team, int *ret, ReduceArgs &r, std::string &why)
+{
+    if (team_args(s, team, r, why)) return 1;
+    r.ret = ret;
+    return 0;
+}
 
 // Work captured into a hipGraph runs when the graph is launched: ordering it against other
 // collectives is the caller's (launch order), so captured calls neither wait nor mark.
@@ -910,6 +973,16 @@ int mark_stream(State &s, hipStream_t st)
     s.last_stream = st;
     s.last_stream_set = true;
     return 0;
+}
+
+// Epilogue of every host collective: the ordering mark, and for a blocking call the wait for its
+// stream and the team's device-side timeouts.
+int finish_call(State &s, int team, hipStream_t st, bool blocking)
+{
+    if (mark_stream(s, st)) return 1;
+    if (!blocking) return 0;
+    if (host_wait(s, st)) return 1;
+    return check_team_errors(s, team);
 }
 
 int staging_acquire(State &s, hipStream_t st)
@@ -1078,19 +1151,19 @@ int reduce_heap(State &s, int team, int op, int dt, void *dst, const void *src, 
             return 0;
         };
         if (mark(0)) return 1;
-        if (team_barrier(s, team, a, st)) return 1;
+        if (team_barrier(a, st)) return 1;
         if (mark(1)) return 1;
         HIP_TRY(launch_rs_phase(op, dt, ph, st));
         if (mark(2)) return 1;
         if (!direct) {
-            if (team_barrier(s, team, a, st)) return 1;
+            if (team_barrier(a, st)) return 1;
             if (mark(3)) return 1;
             HIP_TRY(launch_ag_phase(ph, st));
         } else if (mark(3)) {
             return 1;
         }
         if (mark(4)) return 1;
-        if (team_barrier(s, team, a, st)) return 1;
+        if (team_barrier(a, st)) return 1;
         if (mark(5)) return 1;
         if (inplace_fold && launch_copy(dst, scratch, nb, st)) return 1;
         s.phase_recorded = s.phase_recorded || ev;
@@ -1115,23 +1188,17 @@ int reduce_heap(State &s, int team, int op, int dt, void *dst, const void *src, 
 // buffers, and ranges HIP refuses (e.g. already registered), keep the synchronous copies.
 constexpr size_t kPinMinBytes = (size_t) 1 << 20;
 
-bool pageable_host(const void *p)
-{
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void) hipGetLastError();
-        return true;
-    }
-    return attr.type == hipMemoryTypeUnregistered || (attr.type == hipMemoryTypeHost && attr.devicePointer == nullptr);
-}
-
 struct CallPins {
     void *pinned[2] = {nullptr, nullptr};
-    void pin(void *p, size_t bytes)
+    // `info`: the call's PtrInfo of `p`; emptied when `p` gets registered, which changes the answer.
+    void pin(const State &s, void *p, size_t bytes, PtrInfo &info)
     {
-        if (!p || bytes < kPinMinBytes || !pageable_host(p)) return;
+        if (!p || bytes < kPinMinBytes || !ptr_info(s, p, info).pageable()) return;
         for (void *q : pinned)
-            if (q == p) return;  // in place: one registration
+            if (q == p) {  // in place: one registration (and `info` predates it)
+                info = PtrInfo{};
+                return;
+            }
         const hipError_t e = hipHostRegister(p, bytes, hipHostRegisterDefault);
         if (e != hipSuccess) {
             (void) hipGetLastError();
@@ -1143,6 +1210,7 @@ struct CallPins {
         if (debug_level() > 1)
             fprintf(stderr, "[ishmem_amd] page-locked %p, %zu bytes for the call\n", p, bytes);
         (pinned[0] ? pinned[1] : pinned[0]) = p;
+        info = PtrInfo{};
     }
     bool any() const { return pinned[0] || pinned[1]; }
     // After the call's last copy has completed (the caller synchronises first).
@@ -1162,13 +1230,13 @@ struct CallPins {
 // and chunk k-1's copy-out overlap chunk k's collective (PCIe is full duplex).  Replaces the
 // synchronous 64 KiB bounce loop ishmemi_generic_op_reduce (src/collectives/reduce_impl.h:186-228).
 int reduce_staged_pipeline(State &s, int team, int op, int dt, void *dst, const void *src, size_t n,
-                           int *ret, hipStream_t st);
+                           int *ret, hipStream_t st, PtrInfo &di, PtrInfo &si);
 
 // The pipeline, with pageable host buffers page-locked for the call.  A call that pinned a buffer
 // completes before it returns (the buffers are unlocked after their last copy), which a pageable
-// buffer's synchronous copies would have made it do anyway.
+// buffer's synchronous copies would have made it do anyway.  di / si: the call's PtrInfo of dst / src.
 int reduce_staged(State &s, int team, int op, int dt, void *dst, const void *src, size_t n, int *ret,
-                  hipStream_t st)
+                  hipStream_t st, PtrInfo &di, PtrInfo &si)
 {
     const size_t bytes = n * dtype_size(dt);
     CallPins pins;
@@ -1176,10 +1244,10 @@ int reduce_staged(State &s, int team, int op, int dt, void *dst, const void *src
     // invalidate the capture, and the buffers would be unlocked again before any replay.  The
     // captured copies then stay HIP's own pageable copies.
     if (!capturing(st)) {
-        pins.pin(const_cast<void *>(src), bytes);
-        pins.pin(dst, bytes);
+        pins.pin(s, const_cast<void *>(src), bytes, si);
+        pins.pin(s, dst, bytes, di);
     }
-    int rc = reduce_staged_pipeline(s, team, op, dt, dst, src, n, ret, st);
+    int rc = reduce_staged_pipeline(s, team, op, dt, dst, src, n, ret, st, di, si);
     if (pins.any()) {
         // Every copy of the call has completed (also after a failure part-way) before unlocking.
         bool ok = hipStreamSynchronize(st) == hipSuccess;
@@ -1191,24 +1259,12 @@ int reduce_staged(State &s, int team, int op, int dt, void *dst, const void *src
     return rc;
 }
 
-// Device address of host memory the GPU can load / store directly (hipHostMalloc'd, or registered
-// by the caller or by CallPins), else null.
-char *host_device_view(const void *p)
-{
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void) hipGetLastError();
-        return nullptr;
-    }
-    return attr.type == hipMemoryTypeHost ? (char *) attr.devicePointer : nullptr;
-}
-
 int reduce_staged_pipeline(State &s, int team, int op, int dt, void *dst, const void *src, size_t n,
-                           int *ret, hipStream_t st)
+                           int *ret, hipStream_t st, PtrInfo &di, PtrInfo &si)
 {
     const size_t es = dtype_size(dt);
-    const char *src_dev = (s.staged_copy_kernel & 2) ? host_device_view(src) : nullptr;
-    char *dst_dev = (s.staged_copy_kernel & 1) ? host_device_view(dst) : nullptr;
+    const char *src_dev = (s.staged_copy_kernel & 2) ? ptr_info(s, src, si).host_view() : nullptr;
+    char *dst_dev = (s.staged_copy_kernel & 1) ? ptr_info(s, dst, di).host_view() : nullptr;
     const int nslots = s.staging_slots;
     const size_t slot_bytes = (s.staging_bytes / (size_t) nslots) & ~(kHeapAlign - 1);
     const size_t chunk = (slot_bytes / es) & ~size_t(63);
@@ -1307,30 +1363,16 @@ int collect_launch(State &s, int team, void *dst, const void *src, const uint64_
         // Large: barrier, one-shot pull grid, barrier (kernels_coll.hip collect_phase_kernel).
         // Decided on the total bytes only, which every member knows, so all take the same path.
         ReduceArgs r;
-        if (team_args(s, team, r, why)) return fail("collect: " + why);
-        r.ret = ret;
-        if (team_barrier(s, team, r, st)) return 1;
+        if (barrier_args(s, team, ret, r, why)) return fail("collect: " + why);
+        if (team_barrier(r, st)) return 1;
         HIP_TRY(launch_collect_phase(a, st));
-        if (team_barrier(s, team, r, st)) return 1;
+        if (team_barrier(r, st)) return 1;
         return 0;
     }
     const uint64_t items = maxb / a.unit, tile = (uint64_t) kBlock * kUnroll;
     const int grid = (int) std::max<uint64_t>(1, std::min<uint64_t>((items + tile - 1) / tile, s.max_blocks));
     HIP_TRY(launch_collect(a, grid, st));
     return 0;
-}
-
-// Memory a kernel of this device may write: the heap, device memory, pinned host memory.
-bool device_writable(const State &s, const void *p)
-{
-    if (in_heap(s, p)) return true;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void) hipGetLastError();
-        return false;  // pageable host memory
-    }
-    return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged ||
-           (attr.type == hipMemoryTypeHost && attr.devicePointer != nullptr);
 }
 
 // fcollect / collect with a source outside the heap (host or plain device memory, which peers
@@ -1372,9 +1414,7 @@ int collect_on_stream_impl(int team, void *dst, const void *src, size_t nbytes, 
 {
     State &s = S();
     std::lock_guard<std::mutex> lk(s.mu);
-    if (!s.initialized) return fail("collect: not initialized");
-    if (team < 0 || team >= kMaxTeams || !s.teams[team].valid || s.teams[team].my_idx < 0)
-        return fail("collect: invalid team or caller not a member");
+    if (team_call(s, "collect", team)) return 1;
     Team &t = s.teams[team];
     if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));
     if (t.size == 1) {
@@ -1418,15 +1458,14 @@ int fcollect_impl(int team, void *dst, const void *src, size_t nbytes, int *ret,
 {
     State &s = S();
     std::lock_guard<std::mutex> lk(s.mu);
-    if (!s.initialized) return fail("fcollect: not initialized");
-    if (team < 0 || team >= kMaxTeams || !s.teams[team].valid || s.teams[team].my_idx < 0)
-        return fail("fcollect: invalid team or caller not a member");
+    if (team_call(s, "fcollect", team)) return 1;
     Team &t = s.teams[team];
     if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));  // sticky: launches OR failures in
     if (t.size == 1) {
         if (nbytes && dst != src && launch_copy(dst, src, nbytes, st)) return 1;
     } else {
-        if (!device_writable(s, dst)) return fail("fcollect: dest must be heap, device or pinned host memory");
+        // staged >= 0: the blocking call has asked about dest already and exchanged the answer.
+        if (staged < 0 && !device_writable(s, dst)) return fail("fcollect: dest must be heap, device or pinned host memory");
         uint64_t nb[kMaxPes];
         for (int j = 0; j < t.size; ++j) nb[j] = nbytes;
         // A source outside the heap is staged (the staged call is several launches, so the members
@@ -1449,12 +1488,7 @@ int fcollect_impl(int team, void *dst, const void *src, size_t nbytes, int *ret,
             return 1;
         }
     }
-    if (mark_stream(s, st)) return 1;
-    if (blocking) {
-        if (host_wait(s, st)) return 1;
-        if (check_team_errors(s, team)) return 1;
-    }
-    return 0;
+    return finish_call(s, team, st, blocking);
 }
 
 // One u64 per member, in team order, on every member (an 8-byte fcollect through the team
@@ -1462,7 +1496,6 @@ int fcollect_impl(int team, void *dst, const void *src, size_t nbytes, int *ret,
 // anything that must match across members is launched (a member that failed alone would leave
 // its peers waiting for launches that never come).  Called without the state lock.
 constexpr uint64_t kAgreeStaged = 1ull << 62, kAgreeFail = 1ull << 63;
-bool member_call(const State &s, int team);
 
 // The agreement step of the blocking fcollect / collect / scan / broadcast (staged path, counts,
 // argument failures): an allgather of one u64 per member, before anything else is launched.
@@ -1471,18 +1504,10 @@ bool member_call(const State &s, int team);
 // launch completes — no copy in or out.  Round 3 used a synchronous H2D copy, a whole fcollect
 // launch (start and done handshakes) and a synchronous D2H copy (the exchange roughly
 // doubled a small blocking fcollect / scan; BASELINE.md round 4 has the before / after).
-int team_exchange(int team, uint64_t mine, uint64_t *all)
+// *any: the OR of the members' words (the agreed flags); all: every member's word, or null.
+int team_exchange(int team, uint64_t mine, uint64_t *all, uint64_t *any)
 {
     State &s = S();
-#ifdef ISHMEMI_EXCHANGE_VIA_FCOLLECT  // round-3 exchange (A/B builds only)
-    const int p = s.teams[team].size;
-    if (hipMemcpy(s.team_scratch, &mine, 8, hipMemcpyHostToDevice) != hipSuccess)
-        return fail("team exchange: copy failed");
-    if (fcollect_impl(team, s.team_scratch + 64, s.team_scratch, 8, nullptr, 0, true, 0)) return 1;
-    if (hipMemcpy(all, s.team_scratch + 64, 8 * (size_t) p, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail("team exchange: copy failed");
-    return 0;
-#else
     std::lock_guard<std::mutex> lk(s.mu);
     if (!member_call(s, team)) return fail("team exchange: invalid team or caller not a member");
     const Team &t = s.teams[team];
@@ -1496,20 +1521,16 @@ int team_exchange(int team, uint64_t mine, uint64_t *all)
         if (reduce_ll(s, team, ISHMEMI_OP_SUM, ISHMEMI_DT_UINT64, s.exch_dev + kMaxPes, s.exch_dev, 8 * (size_t) p,
                       nullptr, 0))
             return 1;
-        if (mark_stream(s, 0)) return 1;
-        if (host_wait(s, 0)) return 1;
-        if (check_team_errors(s, team)) return 1;
+        if (finish_call(s, team, 0, true)) return 1;
     } else {
         dst[0] = mine;
     }
-    for (int j = 0; j < p; ++j) all[j] = dst[j];
+    *any = 0;
+    for (int j = 0; j < p; ++j) {
+        *any |= dst[j];
+        if (all) all[j] = dst[j];
+    }
     return 0;
-#endif
-}
-
-bool member_call(const State &s, int team)
-{
-    return s.initialized && team >= 0 && team < kMaxTeams && s.teams[team].valid && s.teams[team].my_idx >= 0;
 }
 
 // ---------------- alltoall (ishmem_alltoall, src/collectives/alltoall_impl.h) ----------------
@@ -1553,9 +1574,7 @@ int alltoall_impl(int team, void *dst, const void *src, size_t nbytes, int *ret,
 {
     State &s = S();
     std::lock_guard<std::mutex> lk(s.mu);
-    if (!s.initialized) return fail("alltoall: not initialized");
-    if (team < 0 || team >= kMaxTeams || !s.teams[team].valid || s.teams[team].my_idx < 0)
-        return fail("alltoall: invalid team or caller not a member");
+    if (team_call(s, "alltoall", team)) return 1;
     Team &t = s.teams[team];
     if (nbytes > 0 && (!dst || !src)) return fail("alltoall: null buffer");
     if (t.size > 1 && nbytes > 0 && !checked) {
@@ -1581,12 +1600,7 @@ int alltoall_impl(int team, void *dst, const void *src, size_t nbytes, int *ret,
         }
         if (collect_launch(s, team, dst, nullptr, nb, ret, st, off, srcs)) return 1;
     }
-    if (mark_stream(s, st)) return 1;
-    if (blocking) {
-        if (host_wait(s, st)) return 1;
-        if (check_team_errors(s, team)) return 1;
-    }
-    return 0;
+    return finish_call(s, team, st, blocking);
 }
 
 // ---------------- put / get (ishmem_put / ishmem_get, src/rma.cpp, src/rma_impl.h) ----------------
@@ -1603,19 +1617,86 @@ int alltoall_impl(int team, void *dst, const void *src, size_t nbytes, int *ret,
 //   on_stream - the kernel on the caller's stream.
 enum RmaKind { kRmaBlocking = 0, kRmaNbi = 1, kRmaOnStream = 2 };
 
-// The address a kernel of this device uses for `p` (heap, device, managed or pinned / registered
-// host memory); nullptr for memory it cannot reach (pageable host memory).
-char *device_view(const State &s, const void *p)
+// Argument checks shared by the point-to-point calls (put / get, strided, put_signal, signal
+// operations, AMOs); `what` is the call's name as it appears in its messages.
+int check_pe(const State &s, const std::string &what, int pe)
 {
-    if (in_heap(s, p)) return (char *) p;
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
-        (void) hipGetLastError();
+    if (pe >= 0 && pe < s.npes) return 0;
+    return fail(what + ": pe " + std::to_string(pe) + " outside [0, " + std::to_string(s.npes) + ")");
+}
+
+int check_sig_op(const std::string &what, int sig_op)
+{
+    if (sig_op == kSignalSet || sig_op == kSignalAdd) return 0;
+    return fail(what + ": sig_op " + std::to_string(sig_op) + " is neither ISHMEM_SIGNAL_SET nor ISHMEM_SIGNAL_ADD");
+}
+
+// Heap address `p` of this PE as mapped here for PE `pe`; null (and the error set) if that heap is not mapped.
+char *peer_address(const State &s, const std::string &what, const void *p, int pe)
+{
+    char *remote = translate(s, p, pe);
+    if (!remote) fail(what + ": heap of PE " + std::to_string(pe) + " not mapped");
+    return remote;
+}
+
+// The same for a range: `side` ("dest" / "source") must lie inside the heap for all `bytes` of its
+// `span` ("length" / "extent").
+char *peer_range(const State &s, const std::string &what, const char *side, const char *span, const void *p,
+                 uint64_t bytes, int pe)
+{
+    if (!in_heap(s, p) || bytes > (uint64_t) (s.heap + s.heap_size - (const char *) p)) {
+        fail(what + ": " + side + " is not inside the symmetric heap for its whole " + span);
         return nullptr;
     }
-    if (attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged) return (char *) p;
-    if (attr.type == hipMemoryTypeHost && attr.devicePointer) return (char *) attr.devicePointer;
-    return nullptr;
+    return peer_address(s, what, p, pe);
+}
+
+// The contiguous copy kernel's split: bytes up to dst's next 16-B boundary, 16-B items, the rest.
+RmaArgs rma_args(char *dst, const char *src, size_t nbytes)
+{
+    RmaArgs a{};
+    a.dst = dst;
+    a.src = src;
+    a.head = std::min<uint64_t>(nbytes, (16 - ((uintptr_t) a.dst & 15)) & 15);
+    a.nitems = (nbytes - a.head) / 16;
+    a.tail = nbytes - a.head - a.nitems * 16;
+    return a;
+}
+
+// The stream a call of `kind` runs on: the null stream, the library's _nbi stream (created by the
+// first _nbi call), or the caller's (ordered after the previous collective, order_stream).
+int rma_kind_stream(State &s, RmaKind kind, hipStream_t user, hipStream_t &st)
+{
+    st = nullptr;
+    if (kind == kRmaNbi) {
+        if (!s.rma_stream && hipStreamCreateWithFlags(&s.rma_stream, hipStreamNonBlocking) != hipSuccess)
+            return fail("_nbi: cannot create the library's stream");
+        st = s.rma_stream;
+    } else if (kind == kRmaOnStream) {
+        st = user;
+        return order_stream(s, st);
+    }
+    return 0;
+}
+
+int rma_kind_finish(State &s, RmaKind kind, hipStream_t st)
+{
+    if (kind == kRmaNbi) {
+        s.rma_pending = true;
+        return 0;
+    }
+    if (kind == kRmaOnStream) return mark_stream(s, st);
+    return host_wait(s, st);
+}
+
+// Makes `st` wait for everything enqueued on the _nbi stream so far (a non-blocking stream, which
+// no other stream serialises behind by itself).
+int drain_nbi_into(State &s, hipStream_t st)
+{
+    if (!s.rma_ev) HIP_TRY(hipEventCreateWithFlags(&s.rma_ev, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(s.rma_ev, s.rma_stream));
+    HIP_TRY(hipStreamWaitEvent(st, s.rma_ev, 0));
+    return 0;
 }
 
 int rma_impl(bool put, void *dest, const void *source, size_t nbytes, int pe, RmaKind kind, hipStream_t user)
@@ -1624,15 +1705,11 @@ int rma_impl(bool put, void *dest, const void *source, size_t nbytes, int pe, Rm
     State &s = S();
     std::lock_guard<std::mutex> lk(s.mu);
     if (!s.initialized) return fail(what + ": not initialized");
-    if (pe < 0 || pe >= s.npes)
-        return fail(what + ": pe " + std::to_string(pe) + " outside [0, " + std::to_string(s.npes) + ")");
+    if (check_pe(s, what, pe)) return 1;
     if (nbytes == 0) return 0;
     if (!dest || !source) return fail(what + ": null pointer with nbytes > 0");
-    const char *sym = put ? (const char *) dest : (const char *) source;
-    if (!in_heap(s, sym) || nbytes > (size_t) (s.heap + s.heap_size - sym))
-        return fail(what + (put ? ": dest" : ": source") + " is not inside the symmetric heap for its whole length");
-    char *remote = translate(s, sym, pe);
-    if (!remote) return fail(what + ": heap of PE " + std::to_string(pe) + " not mapped");
+    char *remote = peer_range(s, what, put ? "dest" : "source", "length", put ? dest : source, nbytes, pe);
+    if (!remote) return 1;
     char *local = device_view(s, put ? source : dest);
     if (!local) {
         if (kind != kRmaBlocking)
@@ -1642,27 +1719,10 @@ int rma_impl(bool put, void *dest, const void *source, size_t nbytes, int pe, Rm
         else HIP_TRY(hipMemcpy(dest, remote, nbytes, hipMemcpyDeviceToHost));
         return 0;
     }
-    RmaArgs a{};
-    a.dst = put ? remote : local;
-    a.src = put ? local : remote;
-    a.head = std::min<uint64_t>(nbytes, (16 - ((uintptr_t) a.dst & 15)) & 15);
-    a.nitems = (nbytes - a.head) / 16;
-    a.tail = nbytes - a.head - a.nitems * 16;
-    hipStream_t st = 0;
-    if (kind == kRmaNbi) {
-        if (!s.rma_stream) HIP_TRY(hipStreamCreateWithFlags(&s.rma_stream, hipStreamNonBlocking));
-        st = s.rma_stream;
-    } else if (kind == kRmaOnStream) {
-        st = user;
-        if (order_stream(s, st)) return 1;
-    }
-    HIP_TRY(launch_rma_copy(a, put, s.max_blocks, st));
-    if (kind == kRmaNbi) {
-        s.rma_pending = true;
-        return 0;
-    }
-    if (kind == kRmaOnStream) return mark_stream(s, st);
-    return host_wait(s, st);
+    hipStream_t st = nullptr;
+    if (rma_kind_stream(s, kind, user, st)) return 1;
+    HIP_TRY(launch_rma_copy(rma_args(put ? remote : local, put ? local : remote, nbytes), put, s.max_blocks, st));
+    return rma_kind_finish(s, kind, st);
 }
 
 // ---------------- strided / blocked put / get --------------------------------------
@@ -1683,8 +1743,7 @@ int strided_impl(bool put, void *dest, const void *source, ptrdiff_t dst, ptrdif
         if (!s.initialized) return fail(what + ": not initialized");
         if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8 && elem_bytes != 16)
             return fail(what + ": elem_bytes " + std::to_string(elem_bytes) + " is not 1, 2, 4, 8 or 16");
-        if (pe < 0 || pe >= s.npes)
-            return fail(what + ": pe " + std::to_string(pe) + " outside [0, " + std::to_string(s.npes) + ")");
+        if (check_pe(s, what, pe)) return 1;
         if (dst < 1 || sst < 1)
             return fail(what + ": stride " + std::to_string(dst < 1 ? dst : sst) + " is not positive (strides are >= 1)");
         if ((uint64_t) dst < bsize || (uint64_t) sst < bsize)
@@ -1705,11 +1764,8 @@ int strided_impl(bool put, void *dest, const void *source, ptrdiff_t dst, ptrdif
         if (__builtin_mul_overflow((uint64_t) nblocks, (uint64_t) bsize, &payload) ||
             __builtin_mul_overflow(payload, (uint64_t) elem_bytes, &payload))
             return fail(what + ": payload overflows 64 bits");
-        const char *sym = put ? (const char *) dest : (const char *) source;
-        if (!in_heap(s, sym) || ext[put ? 0 : 1] > (uint64_t) (s.heap + s.heap_size - sym))
-            return fail(what + (put ? ": dest" : ": source") + " is not inside the symmetric heap for its whole extent");
-        char *remote = translate(s, sym, pe);
-        if (!remote) return fail(what + ": heap of PE " + std::to_string(pe) + " not mapped");
+        char *remote = peer_range(s, what, put ? "dest" : "source", "extent", put ? dest : source, ext[put ? 0 : 1], pe);
+        if (!remote) return 1;
         const void *lp = put ? source : (const void *) dest;
         char *local = device_view(s, lp);
         const uint64_t lext = ext[put ? 1 : 0];
@@ -1728,14 +1784,10 @@ int strided_impl(bool put, void *dest, const void *source, ptrdiff_t dst, ptrdif
             a.nblocks = nblocks;
             a.ipb = ipb;
             a.item = item;
-            hipStream_t st = 0;
-            if (kind == kRmaOnStream) {
-                st = user;
-                if (order_stream(s, st)) return 1;
-            }
+            hipStream_t st = nullptr;
+            if (rma_kind_stream(s, kind, user, st)) return 1;
             HIP_TRY(launch_rma_strided(a, put, s.max_blocks, st));
-            if (kind == kRmaOnStream) return mark_stream(s, st);
-            return host_wait(s, st);
+            return rma_kind_finish(s, kind, st);
         }
     }
     // One contiguous run of nblocks * bsize elements: the contiguous kernel (it takes the lock itself).
@@ -1758,33 +1810,6 @@ const char *sync_word_error(const State &s, const void *p, size_t width)
     return nullptr;
 }
 
-hipStream_t rma_kind_stream(State &s, RmaKind kind, hipStream_t user, int &rc)
-{
-    rc = 0;
-    if (kind == kRmaNbi) {
-        if (!s.rma_stream && hipStreamCreateWithFlags(&s.rma_stream, hipStreamNonBlocking) != hipSuccess) {
-            rc = fail("_nbi: cannot create the library's stream");
-            return nullptr;
-        }
-        return s.rma_stream;
-    }
-    if (kind == kRmaOnStream) {
-        rc = order_stream(s, user);
-        return user;
-    }
-    return nullptr;
-}
-
-int rma_kind_finish(State &s, RmaKind kind, hipStream_t st)
-{
-    if (kind == kRmaNbi) {
-        s.rma_pending = true;
-        return 0;
-    }
-    if (kind == kRmaOnStream) return mark_stream(s, st);
-    return host_wait(s, st);
-}
-
 int put_signal_impl(void *dest, const void *source, size_t nbytes, uint64_t *sig, uint64_t value, int sig_op, int pe,
                     RmaKind kind, hipStream_t user)
 {
@@ -1792,27 +1817,22 @@ int put_signal_impl(void *dest, const void *source, size_t nbytes, uint64_t *sig
     State &s = S();
     std::lock_guard<std::mutex> lk(s.mu);
     if (!s.initialized) return fail(what + ": not initialized");
-    if (pe < 0 || pe >= s.npes)
-        return fail(what + ": pe " + std::to_string(pe) + " outside [0, " + std::to_string(s.npes) + ")");
-    if (sig_op != kSignalSet && sig_op != kSignalAdd)
-        return fail(what + ": sig_op " + std::to_string(sig_op) + " is neither ISHMEM_SIGNAL_SET nor ISHMEM_SIGNAL_ADD");
+    if (check_pe(s, what, pe) || check_sig_op(what, sig_op)) return 1;
     if (const char *e = sync_word_error(s, sig, 8)) return fail(what + ": sig_addr" + e);
-    uint64_t *rsig = (uint64_t *) translate(s, sig, pe);
-    if (!rsig) return fail(what + ": heap of PE " + std::to_string(pe) + " not mapped");
+    uint64_t *rsig = (uint64_t *) peer_address(s, what, sig, pe);
+    if (!rsig) return 1;
     char *remote = nullptr, *local = nullptr;
     if (nbytes) {
         if (!dest || !source) return fail(what + ": null pointer with nbytes > 0");
-        if (!in_heap(s, dest) || nbytes > (size_t) (s.heap + s.heap_size - (const char *) dest))
-            return fail(what + ": dest is not inside the symmetric heap for its whole length");
-        remote = translate(s, dest, pe);
+        remote = peer_range(s, what, "dest", "length", dest, nbytes, pe);
+        if (!remote) return 1;
         local = device_view(s, source);
         if (!local && kind != kRmaBlocking)
             return fail(what + ": source is not device-accessible (heap, device or pinned host memory; pageable host "
                         "memory is accepted by the blocking host forms only)");
     }
-    int rc = 0;
-    hipStream_t st = rma_kind_stream(s, kind, user, rc);
-    if (rc) return 1;
+    hipStream_t st = nullptr;
+    if (rma_kind_stream(s, kind, user, st)) return 1;
     if (nbytes == 0) {
         HIP_TRY(launch_signal_op(rsig, value, sig_op, st));
     } else if (!local) {
@@ -1820,12 +1840,7 @@ int put_signal_impl(void *dest, const void *source, size_t nbytes, uint64_t *sig
         HIP_TRY(hipMemcpy(remote, source, nbytes, hipMemcpyHostToDevice));
         HIP_TRY(launch_signal_op(rsig, value, sig_op, st));
     } else {
-        RmaArgs a{};
-        a.dst = remote;
-        a.src = local;
-        a.head = std::min<uint64_t>(nbytes, (16 - ((uintptr_t) a.dst & 15)) & 15);
-        a.nitems = (nbytes - a.head) / 16;
-        a.tail = nbytes - a.head - a.nitems * 16;
+        const RmaArgs a = rma_args(remote, local, nbytes);
         if ((long long) std::min<size_t>(nbytes, (size_t) std::numeric_limits<long long>::max()) <= s.put_signal_fused_max) {
             HIP_TRY(launch_put_signal(a, rsig, value, sig_op, st));
         } else {
@@ -1841,13 +1856,10 @@ int signal_op_impl(uint64_t *sig, uint64_t value, int sig_op, int pe)
     State &s = S();
     std::lock_guard<std::mutex> lk(s.mu);
     if (!s.initialized) return fail("signal_op: not initialized");
-    if (pe < 0 || pe >= s.npes)
-        return fail("signal_op: pe " + std::to_string(pe) + " outside [0, " + std::to_string(s.npes) + ")");
-    if (sig_op != kSignalSet && sig_op != kSignalAdd)
-        return fail("signal_op: sig_op " + std::to_string(sig_op) + " is neither ISHMEM_SIGNAL_SET nor ISHMEM_SIGNAL_ADD");
+    if (check_pe(s, "signal_op", pe) || check_sig_op("signal_op", sig_op)) return 1;
     if (const char *e = sync_word_error(s, sig, 8)) return fail(std::string("signal_op: sig_addr") + e);
-    uint64_t *rsig = (uint64_t *) translate(s, sig, pe);
-    if (!rsig) return fail("signal_op: heap of PE " + std::to_string(pe) + " not mapped");
+    uint64_t *rsig = (uint64_t *) peer_address(s, "signal_op", sig, pe);
+    if (!rsig) return 1;
     HIP_TRY(launch_signal_op(rsig, value, sig_op, 0));
     return host_wait(s, 0);
 }
@@ -2007,23 +2019,18 @@ int amo_impl(bool nbi, int op, int dt, void *fetch, void *dest, uint64_t value, 
     const std::string what = std::string("atomic_") + kAmoName[op] + (nbi ? "_nbi" : "");
     if (!s.initialized) return fail(what + ": not initialized");
     if (nbi && !amo_fetches(op)) return fail(what + ": only the fetching operations have an _nbi form");
-    if (pe < 0 || pe >= s.npes)
-        return fail(what + ": pe " + std::to_string(pe) + " outside [0, " + std::to_string(s.npes) + ")");
-    int width = 0;
-    switch (dt) {
-        case ISHMEMI_DT_INT32: case ISHMEMI_DT_UINT32: width = 4; break;
-        case ISHMEMI_DT_INT64: case ISHMEMI_DT_UINT64: width = 8; break;
-        case ISHMEMI_DT_FLOAT: case ISHMEMI_DT_DOUBLE:
-            if (op != kAmoFetch && op != kAmoSet && op != kAmoSwap)
-                return fail(what + ": float and double take fetch, set and swap only");
-            width = dt == ISHMEMI_DT_FLOAT ? 4 : 8;
-            break;
-        default:
-            return fail(what + ": dtype " + std::to_string(dt) + " is not a 32- or 64-bit integer type, float or double");
+    if (check_pe(s, what, pe)) return 1;
+    int width = 0, is_signed = 0;
+    if (dt == ISHMEMI_DT_FLOAT || dt == ISHMEMI_DT_DOUBLE) {
+        if (op != kAmoFetch && op != kAmoSet && op != kAmoSwap)
+            return fail(what + ": float and double take fetch, set and swap only");
+        width = dt == ISHMEMI_DT_FLOAT ? 4 : 8;
+    } else if (!sync_dtype(dt, width, is_signed)) {
+        return fail(what + ": dtype " + std::to_string(dt) + " is not a 32- or 64-bit integer type, float or double");
     }
     if (const char *e = sync_word_error(s, dest, (size_t) width)) return fail(what + ": dest" + e);
-    char *remote = translate(s, dest, pe);
-    if (!remote) return fail(what + ": heap of PE " + std::to_string(pe) + " not mapped");
+    char *remote = peer_address(s, what, dest, pe);
+    if (!remote) return 1;
     AmoArgs a{};
     a.dest = remote;
     a.op = op;
@@ -2037,12 +2044,10 @@ int amo_impl(bool nbi, int op, int dt, void *fetch, void *dest, uint64_t value, 
         if (!a.fetch_out)
             return fail(what + ": fetch is not device-accessible (heap, device or pinned host memory; pageable host "
                         "memory is not accepted by _nbi forms)");
-        int rc = 0;
-        hipStream_t st = rma_kind_stream(s, kRmaNbi, nullptr, rc);
-        if (rc) return 1;
+        hipStream_t st = nullptr;
+        if (rma_kind_stream(s, kRmaNbi, nullptr, st)) return 1;
         HIP_TRY(launch_amo(a, st));
-        s.rma_pending = true;
-        return 0;
+        return rma_kind_finish(s, kRmaNbi, st);
     }
     volatile uint64_t *hv = nullptr;
     if (amo_fetches(op)) {
@@ -2051,16 +2056,57 @@ int amo_impl(bool nbi, int op, int dt, void *fetch, void *dest, uint64_t value, 
         *hv = 0;
         a.fetch_out = s.wait_dev + (size_t) kWaitSlots * 64;
     }
-    if (s.rma_pending) {
-        // The null stream does not wait for a non-blocking stream by itself (see above).
-        if (!s.rma_ev) HIP_TRY(hipEventCreateWithFlags(&s.rma_ev, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(s.rma_ev, s.rma_stream));
-        HIP_TRY(hipStreamWaitEvent(0, s.rma_ev, 0));
-    }
+    // The null stream does not wait for a non-blocking stream by itself (see above).
+    if (s.rma_pending && drain_nbi_into(s, 0)) return 1;
     HIP_TRY(launch_amo(a, 0));
     if (host_wait(s, 0)) return 1;
     if (fetched) *fetched = hv ? *hv : 0;
     return 0;
+}
+
+// The scan through scratch rows in the staging region, `seg` elements at a time (the rows of a
+// segment fit the region; member c's rows: [k][chunk c]).
+int scan_scratch(State &s, int team, int dt, int inclusive, void *dst, const void *src, size_t n, uint64_t seg,
+                 int *ret, hipStream_t st)
+{
+    const Team &t = s.teams[team];
+    const size_t es = dtype_size(dt);
+    if (order_stream(s, st) || staging_acquire(s, st)) return 1;
+    for (uint64_t off = 0; off < n; off += seg) {
+        const uint64_t m = std::min<uint64_t>(seg, n - off);
+        ScanArgs a;
+        memset(&a, 0, sizeof(a));
+        std::string why;
+        if (fill_team_sync_args(s, team, a, why)) return fail("scan: " + why);
+        for (int j = 0; j < t.size; ++j) {
+            const int gpe = t.start + j * t.stride;
+            a.src[j] = translate(s, (const char *) src + off * es, gpe);
+            a.scratch[j] = translate(s, s.staging, gpe);
+        }
+        a.dst = (char *) dst + off * es;
+        a.ret = ret;
+        a.nelems = m;
+        a.items_per_chunk = items_per_chunk(m, t.size);
+        a.inclusive = inclusive;
+        const bool vec = (((uintptr_t) dst | (uintptr_t) src | (uintptr_t) s.staging) & 15) == 0;
+        if ((long long) (m * es) >= s.phased_min) {
+            // Large segment: barrier, one-shot fold grid, barrier, one-shot pull grid, barrier
+            // (kernels_coll.hip scan_p1_kernel / scan_p2_kernel).  Every member knows m.
+            ReduceArgs r;
+            if (barrier_args(s, team, ret, r, why)) return fail("scan: " + why);
+            if (team_barrier(r, st)) return 1;
+            HIP_TRY(launch_scan_phase(dt, a, vec, 1, st));
+            if (team_barrier(r, st)) return 1;
+            HIP_TRY(launch_scan_phase(dt, a, vec, 2, st));
+            if (team_barrier(r, st)) return 1;
+            continue;
+        }
+        const uint64_t tile = (uint64_t) kBlock * 2 * (vec ? 16 / es : 1);
+        const int grid = (int) std::max<uint64_t>(
+            1, std::min<uint64_t>((a.items_per_chunk + tile - 1) / tile, s.max_blocks));
+        HIP_TRY(launch_scan(dt, a, vec, grid, st));
+    }
+    return staging_release(s, st);
 }
 
 int scan_impl(int team, int dt, int inclusive, void *dst, const void *src, size_t n, int *ret,
@@ -2068,10 +2114,9 @@ int scan_impl(int team, int dt, int inclusive, void *dst, const void *src, size_
 {
     State &s = S();
     std::lock_guard<std::mutex> lk(s.mu);
-    if (!s.initialized) return fail("scan: not initialized");
-    if (!op_dtype_valid(ISHMEMI_OP_SUM, dt)) return fail("scan: invalid dtype");
-    if (team < 0 || team >= kMaxTeams || !s.teams[team].valid || s.teams[team].my_idx < 0)
-        return fail("scan: invalid team or caller not a member");
+    // The dtype is checked between team_call's two tests, as ever: "not initialized" comes first.
+    if (s.initialized && !op_dtype_valid(ISHMEMI_OP_SUM, dt)) return fail("scan: invalid dtype");
+    if (team_call(s, "scan", team)) return 1;
     Team &t = s.teams[team];
     const size_t es = dtype_size(dt);
     if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));  // sticky over the segments
@@ -2083,25 +2128,19 @@ int scan_impl(int team, int dt, int inclusive, void *dst, const void *src, size_
     } else {
         if (!in_heap(s, dst) || !in_heap(s, src)) return fail("scan: buffers must be symmetric-heap memory");
         if (((uintptr_t) dst | (uintptr_t) src) % es) return fail("scan: misaligned buffers");
-        if (ll_eligible(s, t, dst, src, n * es)) {
-            // Small payloads (round 5): the granule exchange, each member folding members 0..me
-            // (inclusive) or 0..me-1 (exclusive) — no scratch rows, no handshakes.
-            if (reduce_ll(s, team, ISHMEMI_OP_SUM, dt, dst, src, n * es, ret, st, inclusive ? kLLInscan : kLLExscan))
-                return 1;
-            if (mark_stream(s, st)) return 1;
-            if (blocking) {
-                if (host_wait(s, st)) return 1;
-                if (check_team_errors(s, team)) return 1;
-            }
-            return 0;
-        }
         // Segments whose p scratch rows fit the staging region (member c's rows: [k][chunk c]).
         const uint64_t ipc_max = ((s.staging_bytes / es) / (uint64_t) t.size) & ~uint64_t(63);
         const uint64_t seg = ipc_max * (uint64_t) t.size;
-        if (ipc_max == 0) return fail("scan: staging region too small for this team");
         const uintptr_t d0 = (uintptr_t) dst, s0 = (uintptr_t) src, nb = n * es;
         const bool disjoint = d0 + nb <= s0 || s0 + nb <= d0;
-        if (disjoint && (t.size == 2 || (long long) nb <= team_limits(s, t).fold)) {
+        if (ll_eligible(s, t, dst, src, nb)) {
+            // Small payloads (round 5): the granule exchange, each member folding members 0..me
+            // (inclusive) or 0..me-1 (exclusive) — no scratch rows, no handshakes.
+            if (reduce_ll(s, team, ISHMEMI_OP_SUM, dt, dst, src, nb, ret, st, inclusive ? kLLInscan : kLLExscan))
+                return 1;
+        } else if (ipc_max == 0) {
+            return fail("scan: staging region too small for this team");
+        } else if (disjoint && (t.size == 2 || (long long) nb <= team_limits(s, t).fold)) {
             // Two members, disjoint buffers: barrier, direct one-shot fold, barrier (no scratch;
             // kernels_coll.hip scan_direct_kernel).  Every member sees the same n and the same
             // symmetric offsets, so all take this path together.  At every size past the granule
@@ -2120,63 +2159,16 @@ int scan_impl(int team, int dt, int inclusive, void *dst, const void *src, size_
             a.nelems = n;
             a.inclusive = inclusive;
             ReduceArgs r;
-            if (team_args(s, team, r, why)) return fail("scan: " + why);
-            r.ret = ret;
+            if (barrier_args(s, team, ret, r, why)) return fail("scan: " + why);
             const bool vec = ((d0 | s0) & 15) == 0;
-            if (team_barrier(s, team, r, st)) return 1;
+            if (team_barrier(r, st)) return 1;
             HIP_TRY(launch_scan_direct(dt, a, vec, st));
-            if (team_barrier(s, team, r, st)) return 1;
-            if (mark_stream(s, st)) return 1;
-            if (blocking) {
-                if (host_wait(s, st)) return 1;
-                if (check_team_errors(s, team)) return 1;
-            }
-            return 0;
+            if (team_barrier(r, st)) return 1;
+        } else if (scan_scratch(s, team, dt, inclusive, dst, src, n, seg, ret, st)) {
+            return 1;
         }
-        if (order_stream(s, st) || staging_acquire(s, st)) return 1;
-        for (uint64_t off = 0; off < n; off += seg) {
-            const uint64_t m = std::min<uint64_t>(seg, n - off);
-            ScanArgs a;
-            memset(&a, 0, sizeof(a));
-            std::string why;
-            if (fill_team_sync_args(s, team, a, why)) return fail("scan: " + why);
-            for (int j = 0; j < t.size; ++j) {
-                const int gpe = t.start + j * t.stride;
-                a.src[j] = translate(s, (const char *) src + off * es, gpe);
-                a.scratch[j] = translate(s, s.staging, gpe);
-            }
-            a.dst = (char *) dst + off * es;
-            a.ret = ret;
-            a.nelems = m;
-            a.items_per_chunk = items_per_chunk(m, t.size);
-            a.inclusive = inclusive;
-            const bool vec = (((uintptr_t) dst | (uintptr_t) src | (uintptr_t) s.staging) & 15) == 0;
-            if ((long long) (m * es) >= s.phased_min) {
-                // Large segment: barrier, one-shot fold grid, barrier, one-shot pull grid, barrier
-                // (kernels_coll.hip scan_p1_kernel / scan_p2_kernel).  Every member knows m.
-                ReduceArgs r;
-                if (team_args(s, team, r, why)) return fail("scan: " + why);
-                r.ret = ret;
-                if (team_barrier(s, team, r, st)) return 1;
-                HIP_TRY(launch_scan_phase(dt, a, vec, 1, st));
-                if (team_barrier(s, team, r, st)) return 1;
-                HIP_TRY(launch_scan_phase(dt, a, vec, 2, st));
-                if (team_barrier(s, team, r, st)) return 1;
-                continue;
-            }
-            const uint64_t tile = (uint64_t) kBlock * 2 * (vec ? 16 / es : 1);
-            const int grid = (int) std::max<uint64_t>(
-                1, std::min<uint64_t>((a.items_per_chunk + tile - 1) / tile, s.max_blocks));
-            HIP_TRY(launch_scan(dt, a, vec, grid, st));
-        }
-        if (staging_release(s, st)) return 1;
     }
-    if (mark_stream(s, st)) return 1;
-    if (blocking) {
-        if (host_wait(s, st)) return 1;
-        if (check_team_errors(s, team)) return 1;
-    }
-    return 0;
+    return finish_call(s, team, st, blocking);
 }
 
 int team_sync_locked(State &s, int team, hipStream_t st, int *ret)
@@ -2186,10 +2178,8 @@ int team_sync_locked(State &s, int team, hipStream_t st, int *ret)
     if (order_stream(s, st)) return 1;
     ReduceArgs a;
     std::string why;
-    if (team_args(s, team, a, why)) return fail("team_sync: " + why);
-    a.ret = ret;
-    if (team_barrier(s, team, a, st)) return 1;
-    return 0;
+    if (barrier_args(s, team, ret, a, why)) return fail("team_sync: " + why);
+    return team_barrier(a, st);
 }
 
 int reduce_impl(int team, int op, int dt, void *dst, const void *src, size_t n, int *ret,
@@ -2199,8 +2189,7 @@ int reduce_impl(int team, int op, int dt, void *dst, const void *src, size_t n, 
     std::lock_guard<std::mutex> lk(s.mu);
     if (!s.initialized) return fail("reduce: ishmem not initialized");
     if (!op_dtype_valid(op, dt)) return fail("reduce: invalid (op, dtype) pair");
-    if (team < 0 || team >= kMaxTeams || !s.teams[team].valid)
-        return fail("reduce: invalid team handle");
+    if (!valid_team(s, team)) return fail("reduce: invalid team handle");
     Team &t = s.teams[team];
     if (t.my_idx < 0) return fail("reduce: calling PE is not a member of the team");
     if (n > 0 && (!dst || !src)) return fail("reduce: null buffer");
@@ -2208,15 +2197,16 @@ int reduce_impl(int team, int op, int dt, void *dst, const void *src, size_t n, 
     const size_t bytes = n * es;
     // *ret: zeroed once here; every launch of the call ORs a failure into it (sticky).
     if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));
+    PtrInfo di, si;  // dst / src, asked where a path test first needs it and handed down (ptr_info)
 
     if (t.size == 1) {
         // One PE: the reduction is a copy (reduce_impl.h:288-289 with no peers to fold).
         if (n > 0 && dst != src) {
-            const Kind kd = classify(s, dst), ks = classify(s, src);
+            const Kind kd = ptr_info(s, dst, di).kind(), ks = ptr_info(s, src, si).kind();
             if (kd == Kind::Host || ks == Kind::Host) {
                 // Host buffers take the same HBM-staged pipeline as on a multi-PE team, so the
                 // path's host-to-host rate is the one reported in DESIGN.md.
-                if (reduce_staged(s, team, op, dt, dst, src, n, ret, st)) return 1;
+                if (reduce_staged(s, team, op, dt, dst, src, n, ret, st, di, si)) return 1;
             } else if (launch_copy(dst, src, bytes, st)) {
                 return 1;
             }
@@ -2224,20 +2214,15 @@ int reduce_impl(int team, int op, int dt, void *dst, const void *src, size_t n, 
     } else if (n == 0) {
         // The reference still synchronises the team (reduce_impl.h:244, :254).
         if (team_sync_locked(s, team, st, ret)) return 1;
-    } else if (ll_eligible(s, t, dst, src, bytes) && classify(s, dst) != Kind::Host &&
-               classify(s, src) != Kind::Host) {
+    } else if (ll_eligible(s, t, dst, src, bytes) && ptr_info(s, dst, di).kind() != Kind::Host &&
+               ptr_info(s, src, si).kind() != Kind::Host) {
         if (reduce_ll(s, team, op, dt, dst, src, bytes, ret, st)) return 1;
     } else if (in_heap(s, dst) && in_heap(s, src)) {
         if (reduce_heap(s, team, op, dt, dst, src, n, ret, st)) return 1;
     } else {
-        if (reduce_staged(s, team, op, dt, dst, src, n, ret, st)) return 1;
+        if (reduce_staged(s, team, op, dt, dst, src, n, ret, st, di, si)) return 1;
     }
-    if (mark_stream(s, st)) return 1;
-    if (blocking) {
-        if (host_wait(s, st)) return 1;
-        if (check_team_errors(s, team)) return 1;
-    }
-    return 0;
+    return finish_call(s, team, st, blocking);
 }
 
 // Refresh the device copy of the device-API context (after init and after team changes).
@@ -3181,14 +3166,14 @@ int ishmemi_c_heap_info(void **base, size_t *size, size_t *used)
 int ishmemi_c_team_my_pe(int team)
 {
     State &s = S();
-    if (!s.initialized || team < 0 || team >= kMaxTeams || !s.teams[team].valid) return -1;
+    if (!s.initialized || !valid_team(s, team)) return -1;
     return s.teams[team].my_idx;
 }
 
 int ishmemi_c_team_n_pes(int team)
 {
     State &s = S();
-    if (!s.initialized || team < 0 || team >= kMaxTeams || !s.teams[team].valid) return -1;
+    if (!s.initialized || !valid_team(s, team)) return -1;
     return s.teams[team].size;
 }
 
@@ -3443,7 +3428,7 @@ int ishmemi_c_team_get_config(int team, long config_mask, int *num_contexts)
     State &s = S();
     std::lock_guard<std::mutex> lk(s.mu);
     if (!s.initialized) return fail("team_get_config: not initialized");
-    if (team < 0 || team >= kMaxTeams || !s.teams[team].valid) return fail("team_get_config: invalid team");
+    if (!valid_team(s, team)) return fail("team_get_config: invalid team");
     if (config_mask == 0) return 0;
     if (config_mask != 1) return fail("team_get_config: invalid config mask");
     if (!num_contexts) return fail("team_get_config: NULL config with a nonzero mask");
@@ -3456,7 +3441,7 @@ int ishmemi_c_team_set_config(int team, long config_mask, int num_contexts)
     State &s = S();
     std::lock_guard<std::mutex> lk(s.mu);
     if (!s.initialized) return fail("team_set_config: not initialized");
-    if (team < 0 || team >= kMaxTeams || !s.teams[team].valid) return fail("team_set_config: invalid team");
+    if (!valid_team(s, team)) return fail("team_set_config: invalid team");
     if (config_mask != 0 && config_mask != 1) return fail("team_set_config: invalid config mask");
     if (config_mask) s.teams[team].num_contexts = num_contexts;
     return 0;
@@ -3483,11 +3468,10 @@ int ishmemi_c_team_sync(int team)
     State &s = S();
     std::lock_guard<std::mutex> lk(s.mu);
     if (!s.initialized) return fail("team_sync: not initialized");
-    if (team < 0 || team >= kMaxTeams || !s.teams[team].valid) return fail("team_sync: invalid team");
+    if (!valid_team(s, team)) return fail("team_sync: invalid team");
     if (s.teams[team].my_idx < 0) return fail("team_sync: caller not in team");
-    if (team_sync_locked(s, team, 0, nullptr) || mark_stream(s, 0)) return 1;
-    if (host_wait(s, 0)) return 1;
-    return check_team_errors(s, team);
+    if (team_sync_locked(s, team, 0, nullptr)) return 1;
+    return finish_call(s, team, 0, true);
 }
 
 int ishmemi_c_sync_all(void) { return ishmemi_c_team_sync(ISHMEMI_C_TEAM_WORLD); }
@@ -3623,10 +3607,7 @@ int ishmemi_c_quiet_on_stream(void *stream)
     if (capturing(st))
         return fail("quiet_on_stream: _nbi operations are pending and the stream is being captured (call ishmem_quiet "
                     "before the capture)");
-    if (!s.rma_ev) HIP_TRY(hipEventCreateWithFlags(&s.rma_ev, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(s.rma_ev, s.rma_stream));
-    HIP_TRY(hipStreamWaitEvent(st, s.rma_ev, 0));
-    return 0;
+    return drain_nbi_into(s, st);
 }
 
 int ishmemi_c_put_signal(void *dest, const void *source, size_t nbytes, uint64_t *sig, uint64_t value, int sig_op, int pe)
@@ -3843,9 +3824,8 @@ int ishmemi_c_fcollect(int team, void *dest, const void *source, size_t nbytes)
     int staged = -1;
     if (member_call(s, team) && s.teams[team].size > 1 && nbytes > 0) {
         const uint64_t mine = (in_heap(s, source) ? 0 : kAgreeStaged) | (device_writable(s, dest) ? 0 : kAgreeFail);
-        uint64_t all[kMaxPes], any = 0;
-        if (team_exchange(team, mine, all)) return 1;
-        for (int j = 0; j < s.teams[team].size; ++j) any |= all[j];
+        uint64_t any = 0;
+        if (team_exchange(team, mine, nullptr, &any)) return 1;
         if (any & kAgreeFail)
             return fail("fcollect: a member's dest is not device-writable (heap, device or pinned host memory)");
         staged = (any & kAgreeStaged) ? 1 : 0;
@@ -3867,9 +3847,8 @@ int ishmemi_c_alltoall(int team, void *dest, const void *source, size_t nbytes)
     bool checked = false;
     if (member_call(s, team) && s.teams[team].size > 1 && nbytes > 0) {
         const uint64_t e = alltoall_arg_errors(s, s.teams[team], dest, source, nbytes);
-        uint64_t all[kMaxPes], any = 0;
-        if (team_exchange(team, e ? (e | kAgreeFail) : 0, all)) return 1;
-        for (int j = 0; j < s.teams[team].size; ++j) any |= all[j];
+        uint64_t any = 0;
+        if (team_exchange(team, e ? (e | kAgreeFail) : 0, nullptr, &any)) return 1;
         if (any & kAgreeFail) return fail(alltoall_arg_message(any));
         checked = true;
     }
@@ -3889,34 +3868,25 @@ int ishmemi_c_collect(int team, void *dest, const void *source, size_t nbytes)
     // Every member's byte count first (an fcollect of one u64 through the team scratch), then
     // the all-gather at the resulting offsets (src/collectives/collect_impl.h:36-50).
     State &s = S();
-    if (!s.initialized) return fail("collect: not initialized");
-    if (team < 0 || team >= kMaxTeams || !s.teams[team].valid || s.teams[team].my_idx < 0)
-        return fail("collect: invalid team or caller not a member");
+    if (team_call(s, "collect", team)) return 1;
     const int p = s.teams[team].size;
     if (p == 1) return ishmemi_c_fcollect(team, dest, source, nbytes);
     // With the count: kAgreeStaged = that member's source is outside the heap (then every member
     // takes the staged path: peers' sources are only found from a symmetric source address);
     // kAgreeFail = its dest is not device-writable (then every member fails, nothing launched).
     const uint64_t mine = nbytes | (in_heap(s, source) ? 0 : kAgreeStaged) | (device_writable(s, dest) ? 0 : kAgreeFail);
-    uint64_t counts[kMaxPes];
-    if (team_exchange(team, mine, counts)) return 1;
-    bool staged = false, failed = false;
-    for (int j = 0; j < p; ++j) {
-        staged = staged || (counts[j] & kAgreeStaged);
-        failed = failed || (counts[j] & kAgreeFail);
-        counts[j] &= ~(kAgreeStaged | kAgreeFail);
-    }
-    if (failed) return fail("collect: a member's dest is not device-writable (heap, device or pinned host memory)");
+    uint64_t counts[kMaxPes], any = 0;
+    if (team_exchange(team, mine, counts, &any)) return 1;
+    if (any & kAgreeFail) return fail("collect: a member's dest is not device-writable (heap, device or pinned host memory)");
+    for (int j = 0; j < p; ++j) counts[j] &= ~(kAgreeStaged | kAgreeFail);
     std::lock_guard<std::mutex> lk(s.mu);
-    if (staged) {
+    if (any & kAgreeStaged) {
         if (order_stream(s, 0) || collect_staged(s, team, (char *) dest, (const char *) source, counts, nullptr, 0))
             return 1;
     } else if (collect_launch(s, team, dest, source, counts, nullptr, 0)) {
         return 1;
     }
-    if (mark_stream(s, 0)) return 1;
-    if (host_wait(s, 0)) return 1;
-    return check_team_errors(s, team);
+    return finish_call(s, team, 0, true);
 }
 
 int ishmemi_c_collect_on_stream(int team, void *dest, const void *source, size_t nbytes, int *ret,
@@ -3939,9 +3909,8 @@ int ishmemi_c_scan(int team, int dtype, int inclusive, void *dest, const void *s
     if (!member_call(s, team) || nelems == 0 || s.teams[team].size == 1 || !op_dtype_valid(ISHMEMI_OP_SUM, dtype))
         return scan_impl(team, dtype, inclusive, dest, source, nelems, nullptr, 0, true);
     const uint64_t mine = (in_heap(s, source) && in_heap(s, dest)) ? 0 : kAgreeStaged;
-    uint64_t all[kMaxPes], any = 0;
-    if (team_exchange(team, mine, all)) return 1;
-    for (int j = 0; j < s.teams[team].size; ++j) any |= all[j];
+    uint64_t any = 0;
+    if (team_exchange(team, mine, nullptr, &any)) return 1;
     if (!(any & kAgreeStaged)) return scan_impl(team, dtype, inclusive, dest, source, nelems, nullptr, 0, true);
     char *ts, *td;
     {
@@ -4026,8 +3995,7 @@ int ishmemi_c_broadcast(int team, void *dest, const void *source, size_t nbytes,
     if (me_root) mine = in_heap(s, source) ? (uint64_t) ((const char *) source - s.heap) : kAgreeStaged;
     if (nbytes && !device_writable(s, dest)) mine |= kAgreeFail;
     uint64_t all[kMaxPes], any = 0;
-    if (team_exchange(team, mine, all)) return 1;
-    for (int j = 0; j < p; ++j) any |= all[j];
+    if (team_exchange(team, mine, all, &any)) return 1;
     if (any & kAgreeFail) return fail("broadcast: a member's dest is not device-writable (heap, device or pinned host memory)");
     if (nbytes == 0) return ishmemi_c_team_sync(team);
     uint64_t counts[kMaxPes] = {}, zero[kMaxPes] = {};
@@ -4048,9 +4016,7 @@ int ishmemi_c_broadcast(int team, void *dest, const void *source, size_t nbytes,
         for (int j = 0; j < p; ++j) srcs[j] = s.peer_heap[groot] + all[root];
         if (collect_launch(s, team, dest, nullptr, counts, nullptr, 0, zero, srcs)) return 1;
     }
-    if (mark_stream(s, 0)) return 1;
-    if (host_wait(s, 0)) return 1;
-    return check_team_errors(s, team);
+    return finish_call(s, team, 0, true);
 }
 
 int ishmemi_c_scan_on_stream(int team, int dtype, int inclusive, void *dest, const void *source,
