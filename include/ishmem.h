@@ -25,6 +25,7 @@
 
 #include "ishmem_amo.h"
 #include "ishmem_capi.h"
+#include "ishmem_sync.h"
 
 /* ---- version, threading (src/ishmem.h:17-26) ---------------------------------------------- */
 #define ISHMEM_MAJOR_VERSION ISHMEMI_C_SPEC_MAJOR
@@ -617,6 +618,32 @@ inline int ishmem_test(T *ivar, int cmp, T cmp_value)
     inline void ishmem_##TYPENAME##_wait_until(TYPE *ivar, int cmp, TYPE v) { ishmem_wait_until<TYPE>(ivar, cmp, v); } \
     inline int ishmem_##TYPENAME##_test(TYPE *ivar, int cmp, TYPE v) { return ishmem_test<TYPE>(ivar, cmp, v); }
 ISHMEMI_CXX_SYNC_TYPES(ISHMEMI_CXX_SYNC_TYPED)
+
+/* ---- vector waits and tests (src/ishmem.h:1343-1538, src/synchronization.cpp) ---------------------
+ * ishmem_<TN>_wait_until_all / _any / _some and ishmem_<TN>_test_all / _any / _some over `nelems`
+ * variables, their _vector forms with one compare value per element, and the templates, with the
+ * reference's arguments and return types: void (all waits), int (test_all: 1 / 0), size_t (any: the
+ * index or SIZE_MAX; some: the count, indices[0 .. count) ascending).  A nonzero status[i] excludes
+ * element i; status may be null.  status, cmp_values and indices may lie in any memory.  A failure (a
+ * wait that timed out included) leaves its reason in ishmemi_c_last_error() and returns 0 / SIZE_MAX /
+ * 0.  The device-callable forms of the same names are in ishmemx_device.h.  DESIGN.md §3f. */
+namespace ishmemi_cxx {
+template <typename T>
+inline size_t sync_vector(int mode, T *ivars, size_t nelems, size_t *indices, const int *status, int cmp, T cmp_value,
+                          const T *cmp_values)
+{
+    size_t r = 0;
+    (void) ishmemi_c_sync_vector(mode, sync_dtype<T>(), (void *) ivars, nelems, indices, status, cmp, sync_bits(cmp_value),
+                                 (const void *) cmp_values, &r);
+    return r;
+}
+constexpr int kSyncVec = ISHMEMI_C_SYNC_VECTOR;
+}  // namespace ishmemi_cxx
+ISHMEMI_SYNC_VECTOR_GENERIC(inline, ishmemi_cxx)
+#define ISHMEMI_CXX_SYNC_VECTOR_TYPED(TYPENAME, TYPE)                                               \
+    ISHMEMI_SYNC_VECTOR_TYPED_FORM(inline, TYPENAME, TYPE, , TYPE v)                            \
+    ISHMEMI_SYNC_VECTOR_TYPED_FORM(inline, TYPENAME, TYPE, _vector, const TYPE *v)
+ISHMEMI_CXX_SYNC_TYPES(ISHMEMI_CXX_SYNC_VECTOR_TYPED)
 
 /* ---- atomic memory operations (src/ishmem.h:331-640, src/amo.cpp) ----------------------------------
  * ishmem_atomic_<op>[_nbi]<T> and ishmem_<TYPENAME>_atomic_<op>[_nbi], generated by ishmem_amo.h (type

@@ -349,6 +349,47 @@ int ishmemi_c_test(void *ivar, int dtype, int cmp, uint64_t cmp_value_bits, int 
 int ishmemi_c_wait_until_on_stream(void *ivar, int dtype, int cmp, uint64_t cmp_value_bits, uint64_t *value, int *ret,
                                    void *stream);
 
+/* ---- vector waits and tests — ishmem_<TN>_wait_until_all / _any / _some[_vector], ishmem_<TN>_test_all /
+ *      _any / _some[_vector] (src/ishmem.h:1343-1538, src/ishmemx.h:2043-2208, src/synchronization.cpp) ----
+ * `ivars`: `nelems` variables of `dtype` (ISHMEMI_DT_INT32 / UINT32 / INT64 / UINT64) of this PE, aligned,
+ * wholly inside the symmetric heap.  `status` (nelems ints, may be null): a nonzero entry excludes the
+ * element.  Every element is compared `cmp` (in the variable's own type) against `cmp_value_bits`, or,
+ * when `cmp_values` is not null, element i against cmp_values[i] (values of the variables' type): the
+ * _vector form.  ISHMEMI_C_SYNC_VECTOR or-ed into `mode` says that the caller means the _vector form, so
+ * a null cmp_values is refused.  `indices` (nelems size_t): the some modes' output.
+ *   WAIT_ALL   returns once every element of the wait set was seen to satisfy its comparison (each at
+ *              some moment; one seen satisfied is not read again); *result = 1;
+ *   WAIT_ANY   *result = the index of one element that satisfies it; the scan starts behind the index
+ *              the last any call of this PE returned (host and on-stream calls share one rotor);
+ *   WAIT_SOME  returns after the first pass over the set in which an element matched: indices[0 .. count)
+ *              = the elements that matched in that pass, ascending, *result = count; entries from count
+ *              on are not written;
+ *   TEST_ALL / TEST_ANY / TEST_SOME  one pass: *result = 1 / 0, the index or SIZE_MAX, the count (may be 0).
+ * An empty wait set (nelems == 0 or every element excluded) returns at once with 1, SIZE_MAX, 0.
+ * The blocking form accepts status, cmp_values and indices in any memory (pageable host memory is
+ * staged through pinned buffers of the library); indices is written up to count only.  The on-stream
+ * form (the three waits only) reads the arrays when the kernel runs, at every replay of a captured
+ * graph: they, *result and *ret (either may be null) must be device-accessible; *ret = 0, or nonzero if
+ * the wait timed out.  Every wait is bounded by "timeout_ms": the blocking form then returns nonzero
+ * with *result = 0 / SIZE_MAX / 0 and raises ishmemi_c_error_count, the on-stream form sets *ret and
+ * the error count.  When a call reports a match, the data the variables announce is visible to a
+ * kernel launched afterwards.  Argument errors (not initialised, mode, dtype, cmp, ivars null /
+ * misaligned / not wholly inside the heap, indices null for a some mode, cmp_values null for a _vector
+ * form, pageable arrays on a stream) return nonzero before anything is launched and do not move
+ * ishmemi_c_error_count.  Contract: DESIGN.md §3f. */
+#define ISHMEMI_C_SYNC_WAIT_ALL 0
+#define ISHMEMI_C_SYNC_WAIT_ANY 1
+#define ISHMEMI_C_SYNC_WAIT_SOME 2
+#define ISHMEMI_C_SYNC_TEST_ALL 3
+#define ISHMEMI_C_SYNC_TEST_ANY 4
+#define ISHMEMI_C_SYNC_TEST_SOME 5
+#define ISHMEMI_C_SYNC_VECTOR 16
+int ishmemi_c_sync_vector(int mode, int dtype, void *ivars, size_t nelems, size_t *indices, const int *status, int cmp,
+                          uint64_t cmp_value_bits, const void *cmp_values, size_t *result);
+int ishmemi_c_sync_vector_on_stream(int mode, int dtype, void *ivars, size_t nelems, size_t *indices, const int *status,
+                                    int cmp, uint64_t cmp_value_bits, const void *cmp_values, size_t *result, int *ret,
+                                    void *stream);
+
 /* ---- atomic memory operations — ishmem_<TN>_atomic_<op>[_nbi] (src/ishmem.h:331-640, src/amo.cpp,
  *      src/amo_impl.h) ---------------------------------------------------------------------------------
  * One relaxed, system-scope atomic operation `op` (ISHMEMI_C_AMO_*) on the word at `dest` on `pe`
@@ -406,6 +447,7 @@ typedef struct {
     int32_t team_start[ISHMEMI_C_MAX_TEAMS], team_stride[ISHMEMI_C_MAX_TEAMS];
     int32_t team_size[ISHMEMI_C_MAX_TEAMS], team_my_idx[ISHMEMI_C_MAX_TEAMS];
     uint64_t *dev_counts;                         /* symmetric [team][8] u64: device collect counts */
+    uint64_t *sync_rotor;                         /* index the last device wait_until_any / test_any returned */
 } ishmemi_c_device_ctx_t;
 void *ishmemi_c_device_ctx(void);
 /* Device-API context slots: every HIP translation unit that includes ishmemx_device.h owns a

@@ -718,6 +718,68 @@ inline int ishmemx_wait_until_on_stream(T *ivar, int cmp, T cmp_value, hipStream
     }
 ISHMEMI_CXX_SYNC_TYPES(ISHMEMI_CXX_SYNC_ON_STREAM_TYPED)
 
+/* Vector waits on a stream (ishmemx_<TN>_wait_until_all / _any / _some[_vector]_on_queue,
+ * src/ishmemx.h:2043-2208; the reference has no test_*_on_queue): `stream` waits, bounded by the
+ * library's timeout.  *ret (any: the index, some: the count; may be null), status, cmp_values and
+ * indices must be device-accessible: the kernel reads and writes them when it runs, so a captured
+ * call reads their contents at every replay.  A timed-out wait shows in ishmemi_c_error_count() (and in
+ * `*ret` of ishmemi_c_sync_vector_on_stream).  DESIGN.md §3f. */
+namespace ishmemi_cxx {
+template <typename T>
+inline int sync_vector_on_stream(int mode, T *ivars, size_t nelems, size_t *indices, const int *status, int cmp, T cmp_value,
+                                 const T *cmp_values, size_t *ret, hipStream_t stream)
+{
+    return ishmemi_c_sync_vector_on_stream(mode, sync_dtype<T>(), (void *) ivars, nelems, indices, status, cmp,
+                                           sync_bits(cmp_value), (const void *) cmp_values, ret, nullptr, (void *) stream);
+}
+}  // namespace ishmemi_cxx
+/* The three waits of one form, named PREFIX<op>SUFFIX; CV and the trailing arguments: `T v` and
+ * `v, nullptr` (scalar), `const T *v` and `T(), v` (_vector). */
+#define ISHMEMI_CXX_SYNC_VECTOR_ON_STREAM_FORM(TEMPLATE, PREFIX, SUFFIX, T, MODEBITS, CV, ...)                \
+    TEMPLATE inline int PREFIX##wait_until_all##SUFFIX(T *ivars, size_t n, const int *status, int cmp, CV, hipStream_t st) \
+    {                                                                                              \
+        return ishmemi_cxx::sync_vector_on_stream<T>(ISHMEMI_C_SYNC_WAIT_ALL | MODEBITS, ivars, n, nullptr, status, cmp, \
+                                                     __VA_ARGS__, nullptr, st);                    \
+    }                                                                                              \
+    TEMPLATE inline int PREFIX##wait_until_any##SUFFIX(T *ivars, size_t n, const int *status, int cmp, CV, size_t *ret, hipStream_t st) \
+    {                                                                                              \
+        return ishmemi_cxx::sync_vector_on_stream<T>(ISHMEMI_C_SYNC_WAIT_ANY | MODEBITS, ivars, n, nullptr, status, cmp, \
+                                                     __VA_ARGS__, ret, st);                        \
+    }                                                                                              \
+    TEMPLATE inline int PREFIX##wait_until_some##SUFFIX(T *ivars, size_t n, size_t *indices, const int *status, int cmp, CV,   \
+                                              size_t *ret, hipStream_t st)                         \
+    {                                                                                              \
+        return ishmemi_cxx::sync_vector_on_stream<T>(ISHMEMI_C_SYNC_WAIT_SOME | MODEBITS, ivars, n, indices, status, cmp, \
+                                                     __VA_ARGS__, ret, st);                        \
+    }                                                                                              \
+    TEMPLATE inline int PREFIX##wait_until_all##SUFFIX(T *ivars, size_t n, const int *status, int cmp, CV, hipStream_t st,     \
+                                             const hipEvent_t *deps, size_t ndeps, hipEvent_t done) \
+    {                                                                                              \
+        return ishmemi_cxx::with_events(st, deps, ndeps, done, [&] { return PREFIX##wait_until_all##SUFFIX(ivars, n, status, cmp, v, st); }); \
+    }                                                                                              \
+    TEMPLATE inline int PREFIX##wait_until_any##SUFFIX(T *ivars, size_t n, const int *status, int cmp, CV, size_t *ret, hipStream_t st, \
+                                             const hipEvent_t *deps, size_t ndeps, hipEvent_t done) \
+    {                                                                                              \
+        return ishmemi_cxx::with_events(st, deps, ndeps, done,                                     \
+                                        [&] { return PREFIX##wait_until_any##SUFFIX(ivars, n, status, cmp, v, ret, st); }); \
+    }                                                                                              \
+    TEMPLATE inline int PREFIX##wait_until_some##SUFFIX(T *ivars, size_t n, size_t *indices, const int *status, int cmp, CV,   \
+                                              size_t *ret, hipStream_t st, const hipEvent_t *deps, size_t ndeps,    \
+                                              hipEvent_t done)                                     \
+    {                                                                                              \
+        return ishmemi_cxx::with_events(st, deps, ndeps, done,                                     \
+                                        [&] { return PREFIX##wait_until_some##SUFFIX(ivars, n, indices, status, cmp, v, ret, st); }); \
+    }
+ISHMEMI_CXX_SYNC_VECTOR_ON_STREAM_FORM(template <typename T>, ishmemx_, _on_stream, T, 0, T v, v, (const T *) nullptr)
+ISHMEMI_CXX_SYNC_VECTOR_ON_STREAM_FORM(template <typename T>, ishmemx_, _vector_on_stream, T, ISHMEMI_C_SYNC_VECTOR,
+                                       const T *v, T(), v)
+#define ISHMEMI_CXX_SYNC_VECTOR_ON_STREAM_TYPED(TYPENAME, TYPE)                                     \
+    ISHMEMI_CXX_SYNC_VECTOR_ON_STREAM_FORM(, ishmemx_##TYPENAME##_, _on_stream, TYPE, 0, TYPE v, v,              \
+                                           (const TYPE *) nullptr)                                 \
+    ISHMEMI_CXX_SYNC_VECTOR_ON_STREAM_FORM(, ishmemx_##TYPENAME##_, _vector_on_stream, TYPE,                     \
+                                           ISHMEMI_C_SYNC_VECTOR, const TYPE *v, (TYPE) 0, v)
+ISHMEMI_CXX_SYNC_TYPES(ISHMEMI_CXX_SYNC_VECTOR_ON_STREAM_TYPED)
+
 /* Explicit-identity init (the role of ishmemx_init_attr, src/ishmemx.h:21-37). */
 inline int ishmemx_init_pe(int pe, int npes, int device, const char *bootstrap_key)
 {

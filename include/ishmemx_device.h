@@ -51,6 +51,7 @@
 
 #include "ishmem_amo.h"
 #include "ishmem_capi.h"
+#include "ishmem_sync.h"
 
 namespace ishmemx_dev {
 
@@ -884,6 +885,202 @@ __device__ inline T wait_until_group(T *ivar, int cmp, T cmp_value, uint32_t bud
     return (T) (U) bits;
 }
 
+// ---- vector waits and tests from inside a kernel -------------------------------
+// wait_until_all / any / some and test_all / any / some (mode: ISHMEMI_C_SYNC_*, with ISHMEMI_C_SYNC_VECTOR
+// for the per-element compare values) by the group G.  Polls are relaxed system-scope loads of the
+// variable's own width with wait_until_group's back-off and clock check; a test is one pass.
+// Returns all: 1 / 0, any: the index or SIZE_MAX, some: the count.  *st = 0 matched (an empty wait set
+// included), 1 timed out, 2 a test that found nothing.
+constexpr int kSyncVec = ISHMEMI_C_SYNC_VECTOR;
+constexpr uint32_t kSyncMatched = 0, kSyncTimedOut = 1, kSyncNoMatch = 2;
+
+template <typename T>
+__device__ __forceinline__ bool sync_poll_compare(const T *ivars, size_t i, int cmp, T cv)
+{
+    using U = std::conditional_t<sizeof(T) == 8, uint64_t, uint32_t>;
+    const U u = __hip_atomic_load((const U *) ivars + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    return sync_compare<T>((T) u, cmp, cv);
+}
+
+__device__ __forceinline__ bool sync_give_up(const ishmemi_c_device_ctx_t *c, uint32_t it, uint64_t t0)
+{
+    return (it & 15) == 15 && __builtin_amdgcn_s_memrealtime() - t0 > c->timeout_ticks;
+}
+
+__device__ __forceinline__ void sync_backoff(uint32_t it)
+{
+    if (it < 32) __builtin_amdgcn_s_sleep(1);
+    else __builtin_amdgcn_s_sleep(8);
+}
+
+// One lane sweeps the elements itself: no cross-lane operation, so divergent callers are legal.
+template <typename T>
+__device__ inline uint64_t sync_sweep_lane(const ishmemi_c_device_ctx_t *c, int mode, const T *ivars, size_t nelems,
+                                           size_t *indices, const int *status, int cmp, T cmp_value, const T *cmp_values,
+                                           uint32_t *st)
+{
+    const bool test = mode >= ISHMEMI_C_SYNC_TEST_ALL;
+    const int kind = test ? mode - ISHMEMI_C_SYNC_TEST_ALL : mode;  // 0 all, 1 any, 2 some
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+    uint32_t it = 0;
+    *st = kSyncMatched;
+    if (kind == 0) {
+        // In order, each element until it was seen satisfied once; it is not read again.
+        for (size_t i = 0; i < nelems; ++i) {
+            if (status && status[i]) continue;
+            const T cv = cmp_values ? cmp_values[i] : cmp_value;
+            for (;; ++it) {
+                if (sync_poll_compare<T>(ivars, i, cmp, cv)) break;
+                if (test) return *st = kSyncNoMatch, 0;
+                if (sync_give_up(c, it, t0)) return *st = kSyncTimedOut, 0;
+                sync_backoff(it);
+            }
+        }
+        return 1;
+    }
+    size_t start = 0;
+    if (kind == 1 && nelems) {
+        const uint64_t r = __hip_atomic_load(c->sync_rotor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        start = (size_t) ((r % nelems + 1) % nelems);
+    }
+    for (;; ++it) {
+        size_t count = 0, valid = 0;
+        for (size_t k = 0; k < nelems; ++k) {
+            const size_t i = start + k < nelems ? start + k : start + k - nelems;
+            if (status && status[i]) continue;
+            ++valid;
+            if (!sync_poll_compare<T>(ivars, i, cmp, cmp_values ? cmp_values[i] : cmp_value)) continue;
+            if (kind == 1) return i;
+            indices[count++] = i;
+        }
+        if (count) return count;
+        if (valid == 0) return kind == 1 ? (uint64_t) SIZE_MAX : 0;  // empty wait set
+        if (test) return *st = kSyncNoMatch, kind == 1 ? (uint64_t) SIZE_MAX : 0;
+        if (sync_give_up(c, it, t0)) return *st = kSyncTimedOut, kind == 1 ? (uint64_t) SIZE_MAX : 0;
+        sync_backoff(it);
+    }
+}
+
+// The 64 lanes of one full wave sweep together, one element per lane per sub-pass; every decision
+// that ends or continues a loop comes from a ballot or __all and is the same in all lanes.
+template <typename T>
+__device__ inline uint64_t sync_sweep_wave(const ishmemi_c_device_ctx_t *c, int mode, const T *ivars, size_t nelems,
+                                           size_t *indices, const int *status, int cmp, T cmp_value, const T *cmp_values,
+                                           uint32_t *st)
+{
+    const bool test = mode >= ISHMEMI_C_SYNC_TEST_ALL;
+    const int kind = test ? mode - ISHMEMI_C_SYNC_TEST_ALL : mode;
+    const uint32_t lane = __lane_id();
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+    constexpr uint64_t kNone = ~0ull;
+    uint32_t it = 0;
+    *st = kSyncMatched;
+    if (kind == 0) {
+        for (size_t base = 0; base < nelems; base += 64) {
+            const size_t i = base + lane;
+            bool left = i < nelems && !(status && status[i]);
+            const T cv = left && cmp_values ? cmp_values[i] : cmp_value;
+            for (;; ++it) {
+                if (left && sync_poll_compare<T>(ivars, i, cmp, cv)) left = false;
+                if (__all(!left)) break;
+                if (test) return *st = kSyncNoMatch, 0;
+                if (sync_give_up(c, it, t0)) return *st = kSyncTimedOut, 0;
+                sync_backoff(it);
+            }
+        }
+        return 1;
+    }
+    uint64_t start = 0;
+    if (kind == 1 && nelems) {
+        const uint64_t r = __hip_atomic_load(c->sync_rotor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        start = (r % nelems + 1) % nelems;
+    }
+    for (;; ++it) {
+        uint64_t count = 0, best_hi = kNone, best_lo = kNone;
+        bool nonempty = false;
+        for (size_t base = 0; base < nelems; base += 64) {
+            const size_t i = base + lane;
+            const bool ok = i < nelems && !(status && status[i]);
+            const bool match = ok && sync_poll_compare<T>(ivars, i, cmp, cmp_values ? cmp_values[i] : cmp_value);
+            const uint64_t m = __ballot(match);
+            nonempty |= __ballot(ok) != 0;
+            if (m == 0) continue;
+            if (kind == 1) {
+                if (best_lo == kNone) best_lo = base + (uint64_t) __builtin_ctzll(m);
+                uint64_t mh = m;  // the matches at or after `start`
+                if (start > base) mh = start - base >= 64 ? 0 : m & (~0ull << (start - base));
+                if (mh) {
+                    best_hi = base + (uint64_t) __builtin_ctzll(mh);
+                    break;
+                }
+            } else {
+                const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t) (m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t) m, 0));
+                if (match) indices[count + before] = i;
+                count += (uint64_t) __builtin_popcountll(m);
+            }
+        }
+        if (kind == 1 && (best_hi != kNone || best_lo != kNone)) return best_hi != kNone ? best_hi : best_lo;
+        if (kind == 2 && count) return count;
+        const uint64_t none = kind == 1 ? (uint64_t) SIZE_MAX : 0;
+        if (!nonempty) return none;  // empty wait set
+        if (test) return *st = kSyncNoMatch, none;
+        if (sync_give_up(c, it, t0)) return *st = kSyncTimedOut, none;
+        sync_backoff(it);
+    }
+}
+
+// A group of at least one full wave: its first 64 ranks sweep together, the other waves do not poll
+// and meet the sweepers at the group's barrier inside bcast.  A smaller group: the leader sweeps.
+// After a match ONE system-scope acquire, and the sweepers wait for its invalidate BEFORE the
+// broadcast (as wait_until_group does), so every member's plain loads of what the variables announce,
+// and of indices[0 .. count), land behind it.  Every member returns the same value.
+template <typename G, typename T>
+__device__ inline size_t sync_vector_group(int mode_bits, T *ivars, size_t nelems, size_t *indices, const int *status, int cmp,
+                                           T cmp_value, const T *cmp_values)
+{
+    static_assert(std::is_integral_v<T> && (sizeof(T) == 4 || sizeof(T) == 8), "vector waits / tests: 32- or 64-bit integers");
+    const ishmemi_c_device_ctx_t *c = ctx();
+    const int mode = mode_bits & ~kSyncVec;
+    const bool any = mode == ISHMEMI_C_SYNC_WAIT_ANY || mode == ISHMEMI_C_SYNC_TEST_ANY;
+    const bool some = mode == ISHMEMI_C_SYNC_WAIT_SOME || mode == ISHMEMI_C_SYNC_TEST_SOME;
+    uint64_t result = any ? (uint64_t) SIZE_MAX : 0;
+    if (!c) return (size_t) result;
+    if (nelems == 0) return (size_t) (any || some ? result : 1);  // the empty wait set
+    if (cmp < ISHMEMI_C_CMP_EQ || cmp > ISHMEMI_C_CMP_LE || !ivars || (some && !indices) ||
+        ((mode_bits & kSyncVec) && !cmp_values)) {
+        if (G::rank() == 0) record_error(c, kErrBadArgument);
+        return (size_t) result;
+    }
+    const bool wave = !std::is_same_v<G, thread_t> && G::size() >= 64;
+    if (wave ? G::rank() < 64 : G::rank() == 0) {
+        uint32_t st = kSyncMatched;
+        result = wave ? sync_sweep_wave<T>(c, mode, ivars, nelems, indices, status, cmp, cmp_value, cmp_values, &st)
+                      : sync_sweep_lane<T>(c, mode, ivars, nelems, indices, status, cmp, cmp_value, cmp_values, &st);
+        if (st == kSyncMatched && result != (any ? (uint64_t) SIZE_MAX : 0)) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        if (G::rank() == 0) {
+            if (st == kSyncTimedOut) record_error(c, kErrWaitTimeout);
+            if (any && result != (uint64_t) SIZE_MAX)
+                __hip_atomic_store(c->sync_rotor, result, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    if constexpr (!std::is_same_v<G, thread_t>) {
+        const uint32_t lo = G::bcast((uint32_t) result), hi = G::bcast((uint32_t) (result >> 32));
+        result = ((uint64_t) hi << 32) | lo;
+    }
+    return (size_t) result;
+}
+
+// The one work-item form under the name the shared generator (ishmem_sync.h) calls.
+template <typename T>
+__device__ inline size_t sync_vector(int mode_bits, T *ivars, size_t nelems, size_t *indices, const int *status, int cmp,
+                                     T cmp_value, const T *cmp_values)
+{
+    return sync_vector_group<thread_t, T>(mode_bits, ivars, nelems, indices, status, cmp, cmp_value, cmp_values);
+}
+
 template <typename T>
 constexpr bool is_canon()
 {
@@ -1608,6 +1805,70 @@ __device__ inline int ishmemx_test_work_group(T *ivar, int cmp, T cmp_value, con
         return ishmemx_test_work_group<TYPE>(ivar, cmp, v, grp);                                   \
     }
 ISHMEMX_DEV_SYNC_TYPES(ISHMEMX_DEV_SYNC_TYPED)
+
+/* ---- vector waits and tests from a kernel (src/ishmem.h:1343-1538, src/ishmemx.h:1908-2208) --------
+ * ishmem_<TN>_wait_until_all / _any / _some[_vector] and ishmem_<TN>_test_all / _any / _some[_vector],
+ * callable by one work-item (divergent callers are legal), the templates, and their
+ * ishmemx_..._work_group forms for a thread block, a 64-lane tile and the library's tags (same
+ * arguments in every thread; every thread gets the result, and after a some form every thread may
+ * read indices[0 .. count)).  When a call reports a match, plain loads of the data the variables
+ * announce see it, in every thread of the group.  Waits are bounded by the library's timeout: a
+ * timed-out wait returns (any: SIZE_MAX, some: 0) and shows in ishmemi_c_error_count().  An invalid
+ * cmp or a missing array returns at once and is recorded too.  DESIGN.md §3f. */
+ISHMEMI_SYNC_VECTOR_GENERIC(__device__ inline, ishmemx_dev)
+#define ISHMEMX_DEV_SYNC_VECTOR_TYPED(TYPENAME, TYPE)                                               \
+    ISHMEMI_SYNC_VECTOR_TYPED_FORM(__device__ inline, TYPENAME, TYPE, , TYPE v)                     \
+    ISHMEMI_SYNC_VECTOR_TYPED_FORM(__device__ inline, TYPENAME, TYPE, _vector, const TYPE *v)
+ISHMEMX_DEV_SYNC_TYPES(ISHMEMX_DEV_SYNC_VECTOR_TYPED)
+/* The six group operations of one form, named PREFIX<op>SUFFIX; CV and the trailing arguments:
+ * `T v` and `v, nullptr` (scalar), `const T *v` and `T(), v` (_vector). */
+#define ISHMEMX_DEV_SYNC_VECTOR_WG_FORM(TEMPLATE, PREFIX, SUFFIX, T, MODEBITS, CV, ...)             \
+    TEMPLATE __device__ inline void PREFIX##wait_until_all##SUFFIX(T *ivars, size_t n, const int *status, int cmp, CV, \
+                                                                   const Group &)                  \
+    {                                                                                              \
+        (void) ishmemx_dev::sync_vector_group<ishmemx_dev::exec_t<Group>, T>(ISHMEMI_C_SYNC_WAIT_ALL | MODEBITS, ivars, n, \
+                                                                             nullptr, status, cmp, __VA_ARGS__); \
+    }                                                                                              \
+    TEMPLATE __device__ inline size_t PREFIX##wait_until_any##SUFFIX(T *ivars, size_t n, const int *status, int cmp, CV, \
+                                                                     const Group &)                \
+    {                                                                                              \
+        return ishmemx_dev::sync_vector_group<ishmemx_dev::exec_t<Group>, T>(ISHMEMI_C_SYNC_WAIT_ANY | MODEBITS, ivars, n, \
+                                                                             nullptr, status, cmp, __VA_ARGS__); \
+    }                                                                                              \
+    TEMPLATE __device__ inline size_t PREFIX##wait_until_some##SUFFIX(T *ivars, size_t n, size_t *indices, const int *status, \
+                                                                      int cmp, CV, const Group &)  \
+    {                                                                                              \
+        return ishmemx_dev::sync_vector_group<ishmemx_dev::exec_t<Group>, T>(ISHMEMI_C_SYNC_WAIT_SOME | MODEBITS, ivars, n, \
+                                                                             indices, status, cmp, __VA_ARGS__); \
+    }                                                                                              \
+    TEMPLATE __device__ inline int PREFIX##test_all##SUFFIX(T *ivars, size_t n, const int *status, int cmp, CV, const Group &) \
+    {                                                                                              \
+        return (int) ishmemx_dev::sync_vector_group<ishmemx_dev::exec_t<Group>, T>(ISHMEMI_C_SYNC_TEST_ALL | MODEBITS, ivars, \
+                                                                                   n, nullptr, status, cmp, __VA_ARGS__); \
+    }                                                                                              \
+    TEMPLATE __device__ inline size_t PREFIX##test_any##SUFFIX(T *ivars, size_t n, const int *status, int cmp, CV,   \
+                                                               const Group &)                      \
+    {                                                                                              \
+        return ishmemx_dev::sync_vector_group<ishmemx_dev::exec_t<Group>, T>(ISHMEMI_C_SYNC_TEST_ANY | MODEBITS, ivars, n, \
+                                                                             nullptr, status, cmp, __VA_ARGS__); \
+    }                                                                                              \
+    TEMPLATE __device__ inline size_t PREFIX##test_some##SUFFIX(T *ivars, size_t n, size_t *indices, const int *status, \
+                                                                int cmp, CV, const Group &)        \
+    {                                                                                              \
+        return ishmemx_dev::sync_vector_group<ishmemx_dev::exec_t<Group>, T>(ISHMEMI_C_SYNC_TEST_SOME | MODEBITS, ivars, n, \
+                                                                             indices, status, cmp, __VA_ARGS__); \
+    }
+#define ISHMEMX_DEV_TEMPLATE_T_GROUP template <typename T, typename Group>
+#define ISHMEMX_DEV_TEMPLATE_GROUP template <typename Group>
+ISHMEMX_DEV_SYNC_VECTOR_WG_FORM(ISHMEMX_DEV_TEMPLATE_T_GROUP, ishmemx_, _work_group, T, 0, T v, v, (const T *) nullptr)
+ISHMEMX_DEV_SYNC_VECTOR_WG_FORM(ISHMEMX_DEV_TEMPLATE_T_GROUP, ishmemx_, _vector_work_group, T, ISHMEMI_C_SYNC_VECTOR,
+                                const T *v, T(), v)
+#define ISHMEMX_DEV_SYNC_VECTOR_WG_TYPED(TYPENAME, TYPE)                                            \
+    ISHMEMX_DEV_SYNC_VECTOR_WG_FORM(ISHMEMX_DEV_TEMPLATE_GROUP, ishmemx_##TYPENAME##_, _work_group, TYPE, 0, TYPE v, v, \
+                                    (const TYPE *) nullptr)                                        \
+    ISHMEMX_DEV_SYNC_VECTOR_WG_FORM(ISHMEMX_DEV_TEMPLATE_GROUP, ishmemx_##TYPENAME##_, _vector_work_group, TYPE,     \
+                                    ISHMEMI_C_SYNC_VECTOR, const TYPE *v, (TYPE) 0, v)
+ISHMEMX_DEV_SYNC_TYPES(ISHMEMX_DEV_SYNC_VECTOR_WG_TYPED)
 
 /* ---- atomic memory operations from a kernel (src/ishmem.h:331-640) -----------------
  * ishmem_atomic_<op>[_nbi]<T> and ishmem_<TYPENAME>_atomic_<op>[_nbi] (ishmem_amo.h), callable by one

@@ -674,6 +674,63 @@ for _tn in SYNC_TYPENAMES:
         setattr(_mod, _name, _f)
         SIGNAL_NAMES.append(_name)
 del _tn, _name, _f, _nbi, _bits, _is_test
+# ---- vector waits and tests (src/ishmem.h:1343-1538, src/ishmemx.h:2043-2208) --------
+# wait_until_all / any / some and test_all / any / some over `nelems` variables at `ivars`; status /
+# cmp_values / indices are addresses (0 = none) of nelems ints / values of the type / size_t.  A
+# non-zero cmp_values selects the _vector form.
+SYNC_MODES = {"wait_until_all": 0, "wait_until_any": 1, "wait_until_some": 2, "test_all": 3, "test_any": 4, "test_some": 5}
+SYNC_VECTOR_FLAG = 16  # ISHMEMI_C_SYNC_VECTOR: the caller means the _vector form (a zero cmp_values is refused)
+SIZE_MAX = (1 << 64) - 1
+
+
+def sync_vector(mode, dtype: str, ivars: int, nelems: int, indices: int, status: int, cmp: int, cmp_value: int,
+                cmp_values: int = 0) -> tuple[int, int]:
+    """(status, result) — result: all 1 / 0, any the index or SIZE_MAX, some the count.  `mode` is a
+    name from SYNC_MODES or an ISHMEMI_C_SYNC_* code.  Blocking: the arrays may lie in any memory."""
+    r = ctypes.c_size_t(0)
+    rc = _L.ishmemi_c_sync_vector(SYNC_MODES.get(mode, mode), DTYPES.get(dtype, -1), ivars or None, nelems, indices or None,
+                                  status or None, cmp, cmp_value & _U64, cmp_values or None, ctypes.byref(r))
+    return rc, r.value
+
+
+def sync_vector_on_stream(mode, dtype: str, ivars: int, nelems: int, indices: int, status: int, cmp: int, cmp_value: int,
+                          cmp_values: int, result: int, ret: int, stream: int, deps=(), done=None) -> int:
+    """ishmemx_<TN>_wait_until_all / _any / _some[_vector]_on_queue analogue (the waits only); the arrays,
+    *result (any: the index, some: the count) and *ret must be device-accessible (or 0)."""
+    def call(d, s, n, p, st):
+        return _L.ishmemi_c_sync_vector_on_stream(SYNC_MODES.get(mode, mode), DTYPES.get(dtype, -1), ivars or None, nelems,
+                                                  indices or None, status or None, cmp, cmp_value & _U64,
+                                                  cmp_values or None, result or None, ret or None, st)
+    return _rma_on_stream(call, 0, 0, 0, 0, stream, deps, done)
+
+
+def _make_sync_vector(dt: str, op: str, vector: bool):
+    code = SYNC_MODES[op] | (SYNC_VECTOR_FLAG if vector else 0)
+    # the reference's argument order; cv is cmp_value, or the address of cmp_values for a _vector form
+    if op.endswith("some"):
+        def fn(ivars: int, nelems: int, indices: int, status: int, cmp: int, cv: int) -> int:
+            return sync_vector(code, dt, ivars, nelems, indices, status, cmp, 0 if vector else cv, cv if vector else 0)[1]
+    elif op == "wait_until_all":
+        def fn(ivars: int, nelems: int, status: int, cmp: int, cv: int) -> int:
+            return sync_vector(code, dt, ivars, nelems, 0, status, cmp, 0 if vector else cv, cv if vector else 0)[0]
+    else:
+        def fn(ivars: int, nelems: int, status: int, cmp: int, cv: int) -> int:
+            return sync_vector(code, dt, ivars, nelems, 0, status, cmp, 0 if vector else cv, cv if vector else 0)[1]
+    return fn
+
+
+# ishmem_<TN>_<op>[_vector]: 12 typenames x 6 operations x 2 forms.  wait_until_all returns the status
+# (the reference's is void), test_all 1 / 0, the any forms the index or SIZE_MAX, the some forms the count.
+SYNC_VECTOR_NAMES: list[str] = []
+for _tn in SYNC_TYPENAMES:
+    for _op in SYNC_MODES:
+        for _vec in (False, True):
+            _name = f"ishmem_{_tn}_{_op}{'_vector' if _vec else ''}"
+            _f = _make_sync_vector(TYPENAMES[_tn], _op, _vec)
+            _f.__name__ = _name
+            setattr(_mod, _name, _f)
+            SYNC_VECTOR_NAMES.append(_name)
+del _tn, _op, _vec, _name, _f
 # ---- atomic memory operations (src/ishmem.h:331-640, src/amo.cpp; DESIGN.md §3d) --------------------
 # atomic_<op>(dest, dtype, [value], [cond], pe) -> (status, fetched) for the 14 blocking operations and
 # atomic_<op>_nbi(fetch, dest, dtype, [value], [cond], pe) -> status for the 8 fetching ones.  `dtype`

@@ -27,7 +27,7 @@ LIB_TESTHOOKS = PKG / "libishmem_amd_testhooks.so"
 SOURCES = [("kernels.hip", "kernels", []), ("runtime.cpp", "runtime", []),
            ("bootstrap.cpp", "bootstrap", []), ("kernels_coll.hip", "kernels_coll", []),
            ("kernels_rma.hip", "kernels_rma", []), ("kernels_signal.hip", "kernels_signal", []),
-           ("kernels_amo.hip", "kernels_amo", [])] + [
+           ("kernels_amo.hip", "kernels_amo", []), ("kernels_sync.hip", "kernels_sync", [])] + [
     ("kernels_op.hip", f"kernels_op{op}", [f"-DISHMEMI_KOP={op}"]) for op in range(7)]
 ARCH = os.environ.get("ISHMEM_OFFLOAD_ARCH", "gfx950")
 

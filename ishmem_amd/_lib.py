@@ -84,6 +84,8 @@ PROTOTYPES = [
     ("ishmemi_c_wait_until", _i, [_vp, _i, _i, _u64, ctypes.POINTER(_u64)]),
     ("ishmemi_c_test", _i, [_vp, _i, _i, _u64, ctypes.POINTER(_i)]),
     ("ishmemi_c_wait_until_on_stream", _i, [_vp, _i, _i, _u64, _vp, _vp, _vp]),
+    ("ishmemi_c_sync_vector", _i, [_i, _i, _vp, _sz, _vp, _vp, _i, _u64, _vp, ctypes.POINTER(_sz)]),
+    ("ishmemi_c_sync_vector_on_stream", _i, [_i, _i, _vp, _sz, _vp, _vp, _i, _u64, _vp, _vp, _vp, _vp]),
     ("ishmemi_c_amo", _i, [_i, _i, _vp, _u64, _u64, _i, ctypes.POINTER(_u64)]),
     ("ishmemi_c_amo_nbi", _i, [_i, _i, _vp, _vp, _u64, _u64, _i]),
     ("ishmemi_c_stream_wait_events", _i, [_vp, _vp, _sz]),

@@ -387,6 +387,56 @@ struct WaitArgs {
 };
 hipError_t launch_signal_wait(const WaitArgs &a, hipStream_t s);
 
+// Vector waits and tests (kernels_sync.hip): wait_until_all / any / some and
+// test_all / any / some over `nelems` variables of this PE's heap, `width` 4 or 8.  The codes are
+// ISHMEMI_C_SYNC_*.  One wave; lane l owns elements base + u * 64 + l (u < kSyncUnroll) of the current
+// chunk of kSyncChunk elements and reads each with one relaxed system-scope load of its own width.
+constexpr int kSyncWaitAll = 0, kSyncWaitAny = 1, kSyncWaitSome = 2, kSyncTestAll = 3, kSyncTestAny = 4,
+              kSyncTestSome = 5, kSyncModes = 6;
+constexpr int kSyncUnroll = 4;
+constexpr uint64_t kSyncChunk = 64ull * kSyncUnroll;
+__host__ __device__ constexpr bool sync_is_test(int mode) { return mode >= kSyncTestAll; }
+__host__ __device__ constexpr bool sync_is_all(int mode) { return mode == kSyncWaitAll || mode == kSyncTestAll; }
+__host__ __device__ constexpr bool sync_is_any(int mode) { return mode == kSyncWaitAny || mode == kSyncTestAny; }
+__host__ __device__ constexpr bool sync_is_some(int mode) { return mode == kSyncWaitSome || mode == kSyncTestSome; }
+// `status` (nelems ints, may be null): a nonzero entry excludes the element.  `cmp_values` (nelems
+// values of the variables' type) when not null, else `cmp_value` for every element.  `indices`: the
+// some modes' output.  All three are read / written with ordinary loads and stores when the kernel
+// runs (device-accessible addresses).
+//   all:  the chunks are walked in order from element `start` (a multiple of kSyncChunk); bit l of
+//         done_in[u] says that element start + u * 64 + l was seen satisfied by an earlier launch of
+//         the same call and is not read again.  *result_out = 1 when every element of the wait set
+//         was seen satisfied, else 0 with *next_out = the chunk the walk stopped in and done_out[u] =
+//         that chunk's progress (the time-sliced host form passes both to its next launch).
+//   any:  *result_out = the first match in the order rotor + 1, rotor + 2, ... (mod nelems), where
+//         rotor = *rotor when the pointer is not null (else 0); the winner is stored to *rotor.
+//         SIZE_MAX without a match.
+//   some: indices[0 .. count) = the elements that matched in the first pass with a match, ascending;
+//         *result_out = count.
+// A test is one pass.  An empty wait set (nelems == 0 or every element excluded) ends the first pass
+// with kWaitMatched and 1 / SIZE_MAX / 0.  *status_out = kWaitMatched / kWaitTimedOut / kWaitNoMatch is
+// stored after the other results have drained; a timeout also ORs kWaitErrBit into *err.  After a
+// match: one system-scope acquire, before any result is written.
+struct SyncVecArgs {
+    const void *ivars;
+    uint64_t nelems;
+    const int *status;
+    const void *cmp_values;
+    size_t *indices;
+    uint64_t cmp_value;
+    int mode, width, is_signed, cmp;
+    uint64_t start;
+    uint64_t done_in[kSyncUnroll];
+    uint64_t timeout_ticks;
+    uint64_t *rotor;
+    uint64_t *result_out;
+    uint64_t *next_out;
+    uint64_t *done_out;  // kSyncUnroll words
+    int *status_out;
+    uint32_t *err;
+};
+hipError_t launch_sync_vector(const SyncVecArgs &a, hipStream_t s);
+
 // Atomic memory operations (kernels_amo.hip).  The codes are ISHMEMI_C_AMO_*.
 constexpr int kAmoFetch = 0, kAmoSet = 1, kAmoCompareSwap = 2, kAmoSwap = 3, kAmoFetchInc = 4, kAmoInc = 5,
               kAmoFetchAdd = 6, kAmoAdd = 7, kAmoFetchAnd = 8, kAmoAnd = 9, kAmoFetchOr = 10, kAmoOr = 11,

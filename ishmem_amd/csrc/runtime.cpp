@@ -406,7 +406,14 @@ struct State {
     bool wait_busy[kWaitSlots] = {};
     // Line kWaitSlots of the same allocation: the blocking AMOs' fetched value (amo_impl; one word is
     // enough, the call holds s.mu until host_wait returns).
-    char *wait_host = nullptr, *wait_dev = nullptr;  // kWaitSlots + 1 lines of 64 B
+    // Line kWaitSlots + 1: the rotor of the host and on-stream wait_until_any / test_any calls, the
+    // index the last of them returned; the kernel reads and updates it.
+    char *wait_host = nullptr, *wait_dev = nullptr;  // kWaitSlots + 2 lines of 64 B
+    // Vector waits / tests: per wait slot a pinned, mapped buffer through which the blocking forms
+    // stage status / cmp_values / indices arrays that lie in pageable host memory; grown on demand,
+    // released at finalize.
+    char *sync_stage_host[kWaitSlots] = {}, *sync_stage_dev[kWaitSlots] = {};
+    size_t sync_stage_bytes[kWaitSlots] = {};
     // Stream of the previous collective: a collective enqueued on another stream first waits
     // for it, so epochs, flag rows and the staging region are used in call order.
     hipStream_t last_stream = nullptr;
@@ -1895,8 +1902,9 @@ int wait_args(const State &s, const char *what, void *ivar, int dt, int cmp, uin
 int wait_lines(State &s)
 {
     if (s.wait_host) return 0;
-    HIP_TRY(hipHostMalloc((void **) &s.wait_host, (size_t) (kWaitSlots + 1) * 64, hipHostMallocMapped | hipHostMallocCoherent));
+    HIP_TRY(hipHostMalloc((void **) &s.wait_host, (size_t) (kWaitSlots + 2) * 64, hipHostMallocMapped | hipHostMallocCoherent));
     HIP_TRY(hipHostGetDevicePointer((void **) &s.wait_dev, s.wait_host, 0));
+    memset(s.wait_host + (size_t) (kWaitSlots + 1) * 64, 0, 64);  // the any rotor
     return 0;
 }
 
@@ -1991,6 +1999,234 @@ int wait_until_on_stream_impl(void *ivar, int dt, int cmp, uint64_t cmp_bits, ui
     a.status_out = ret;
     a.err = s.err_dev + kMaxTeams;
     HIP_TRY(launch_signal_wait(a, st));
+    return 0;
+}
+
+// ---------------- vector waits and tests -------------------------------------------
+// ishmem_<TN>_wait_until_all / _any / _some[_vector], ishmem_<TN>_test_all / _any / _some[_vector] and
+// the waits' _on_stream forms (src/synchronization.cpp): one sync_vector_kernel launch (kernels_sync.hip)
+// per call, or per 1 ms slice of a blocking wait.
+const char *const kSyncName[kSyncModes] = {"wait_until_all", "wait_until_any", "wait_until_some",
+                                           "test_all",       "test_any",       "test_some"};
+
+// What a call reports when nothing was found, or nothing could be looked for.
+uint64_t sync_no_result(int mode) { return sync_is_any(mode) ? (uint64_t) SIZE_MAX : 0; }
+
+// Validates a call and fills what does not depend on where it runs.  `mode_bits`: ISHMEMI_C_SYNC_* with
+// or without ISHMEMI_C_SYNC_VECTOR; a non-null cmp_values selects the _vector form too.
+int sync_vector_args(const State &s, const std::string &what, int mode_bits, int dt, void *ivars, size_t nelems,
+                     size_t *indices, int cmp, uint64_t cmp_bits, const void *cmp_values, SyncVecArgs &a)
+{
+    if (!s.initialized) return fail(what + ": not initialized");
+    a = SyncVecArgs{};
+    a.mode = mode_bits & ~ISHMEMI_C_SYNC_VECTOR;
+    if (!sync_dtype(dt, a.width, a.is_signed))
+        return fail(what + ": dtype " + std::to_string(dt) + " is not a 32- or 64-bit integer type");
+    if (cmp < kCmpEq || cmp > kCmpLe)
+        return fail(what + ": cmp " + std::to_string(cmp) + " is not one of ISHMEM_CMP_EQ .. ISHMEM_CMP_LE");
+    if (nelems) {
+        if (const char *e = sync_word_error(s, ivars, (size_t) a.width)) return fail(what + ": ivars" + e);
+        if (nelems > (size_t) (s.heap + s.heap_size - (const char *) ivars) / (size_t) a.width)
+            return fail(what + ": ivars + nelems is not inside the symmetric heap");
+        if (sync_is_some(a.mode) && !indices) return fail(what + ": indices is null");
+        if ((mode_bits & ISHMEMI_C_SYNC_VECTOR) && !cmp_values) return fail(what + ": cmp_values is null");
+    }
+    a.ivars = ivars;
+    a.nelems = nelems;
+    a.cmp = cmp;
+    a.cmp_value = cmp_bits;
+    return 0;
+}
+
+// Blocking host form.  *result: all 1 / 0, any the index or SIZE_MAX, some the count.
+int host_sync_vector(int mode_bits, int dt, void *ivars, size_t nelems, size_t *indices, const int *status, int cmp,
+                     uint64_t cmp_bits, const void *cmp_values, uint64_t *result)
+{
+    State &s = S();
+    const int mode = mode_bits & ~ISHMEMI_C_SYNC_VECTOR;
+    if (mode < 0 || mode >= kSyncModes) {
+        if (!s.initialized) return fail("sync_vector: not initialized");
+        return fail("sync_vector: mode " + std::to_string(mode_bits) + " is not one of ISHMEMI_C_SYNC_*");
+    }
+    const std::string what = kSyncName[mode];
+    const bool test = sync_is_test(mode);
+    if (result) *result = sync_no_result(mode);
+    SyncVecArgs a{};
+    int slot = -1;
+    hipStream_t st = nullptr;
+    volatile uint64_t *line = nullptr;
+    volatile int *hs = nullptr;
+    uint64_t total_ticks = 0;
+    size_t *user_indices = nullptr, *staged_indices = nullptr;  // set when indices go through the slot's buffer
+    {
+        std::lock_guard<std::mutex> lk(s.mu);
+        if (sync_vector_args(s, what, mode_bits, dt, ivars, nelems, indices, cmp, cmp_bits, cmp_values, a)) return 1;
+        if (nelems == 0) {  // the empty wait set, known without a launch
+            if (result && sync_is_all(mode)) *result = 1;
+            return 0;
+        }
+        // Where the side arrays live: the kernel reads device-accessible ones in place; pageable ones
+        // are staged through the slot's pinned buffer.
+        struct Side {
+            const void *user;
+            size_t bytes, off;
+            bool staged;
+        } side[3] = {{status, nelems * sizeof(int), 0, false},
+                     {cmp_values, nelems * (size_t) a.width, 0, false},
+                     {sync_is_some(mode) ? indices : nullptr, nelems * sizeof(size_t), 0, false}};
+        const char *const side_name[3] = {"status", "cmp_values", "indices"};
+        char *view[3] = {};
+        size_t need = 0;
+        for (int k = 0; k < 3; ++k) {
+            if (!side[k].user) continue;
+            const PtrInfo info = ptr_info(s, side[k].user);
+            if (info.pageable()) {
+                side[k].staged = true;
+                side[k].off = need;
+                need += (side[k].bytes + 63) & ~(size_t) 63;
+            } else if (!(view[k] = info.view())) {
+                return fail(what + ": " + side_name[k] + " is not device-accessible");
+            }
+        }
+        if (wait_lines(s)) return 1;
+        for (int k = 0; k < kWaitSlots && slot < 0; ++k)
+            if (!s.wait_busy[k]) slot = k;
+        if (slot < 0) return fail(what + ": more than " + std::to_string(kWaitSlots) + " host threads are waiting at once");
+        if (!s.wait_stream[slot]) HIP_TRY(hipStreamCreateWithFlags(&s.wait_stream[slot], hipStreamNonBlocking));
+        if (need > s.sync_stage_bytes[slot]) {
+            // The slot is free, so no kernel is reading the old buffer.
+            if (s.sync_stage_host[slot]) (void) hipHostFree(s.sync_stage_host[slot]);
+            s.sync_stage_host[slot] = s.sync_stage_dev[slot] = nullptr;
+            s.sync_stage_bytes[slot] = 0;
+            const size_t grown = std::max<size_t>(need, 4096);
+            HIP_TRY(hipHostMalloc((void **) &s.sync_stage_host[slot], grown, hipHostMallocMapped | hipHostMallocCoherent));
+            HIP_TRY(hipHostGetDevicePointer((void **) &s.sync_stage_dev[slot], s.sync_stage_host[slot], 0));
+            s.sync_stage_bytes[slot] = grown;
+        }
+        for (int k = 0; k < 3; ++k) {
+            if (!side[k].staged) continue;
+            if (k < 2) memcpy(s.sync_stage_host[slot] + side[k].off, side[k].user, side[k].bytes);
+            view[k] = s.sync_stage_dev[slot] + side[k].off;
+        }
+        if (side[2].staged) {
+            user_indices = indices;
+            staged_indices = (size_t *) (s.sync_stage_host[slot] + side[2].off);
+        }
+        a.status = (const int *) view[0];
+        a.cmp_values = view[1];
+        a.indices = (size_t *) view[2];
+        s.wait_busy[slot] = true;
+        st = s.wait_stream[slot];
+        // The slot's line: {-, status, result, next, done[kSyncUnroll]}.
+        line = (volatile uint64_t *) (s.wait_host + (size_t) slot * 64);
+        hs = (volatile int *) (s.wait_host + (size_t) slot * 64 + 8);
+        char *dline = s.wait_dev + (size_t) slot * 64;
+        a.status_out = (int *) (dline + 8);
+        a.result_out = (uint64_t *) (dline + 16);
+        a.next_out = (uint64_t *) (dline + 24);
+        a.done_out = (uint64_t *) (dline + 32);
+        a.rotor = (uint64_t *) (s.wait_dev + (size_t) (kWaitSlots + 1) * 64);
+        total_ticks = (uint64_t) s.timeout_ms * 100000ull;
+    }
+    int outcome = kWaitNoMatch;
+    std::string hiperr;
+    const auto t0 = std::chrono::steady_clock::now();
+    for (;;) {
+        // As host_wait_until: 1 ms slices, the lock held to launch only.
+        const auto waited = std::chrono::steady_clock::now() - t0;
+        const uint64_t used = (uint64_t) std::chrono::duration_cast<std::chrono::microseconds>(waited).count() * 100ull;
+        a.timeout_ticks = std::min<uint64_t>(kWaitSliceTicks, total_ticks > used ? total_ticks - used : 1);
+        __atomic_store_n((int *) hs, -1, __ATOMIC_RELEASE);
+        hipError_t e;
+        {
+            std::lock_guard<std::mutex> lk(s.mu);
+            e = launch_sync_vector(a, st);
+        }
+        if (e == hipSuccess) {
+            int spins = 0;
+            const auto l0 = std::chrono::steady_clock::now();
+            while (__atomic_load_n((int *) hs, __ATOMIC_ACQUIRE) == -1) {
+                __builtin_ia32_pause();
+                if (++spins == 4096) {
+                    spins = 0;
+                    if (std::chrono::steady_clock::now() - l0 > std::chrono::milliseconds(50)) break;
+                }
+            }
+            if (__atomic_load_n((int *) hs, __ATOMIC_ACQUIRE) == -1) e = hipStreamSynchronize(st);
+        }
+        if (e != hipSuccess) {
+            hiperr = hipGetErrorString(e);
+            break;
+        }
+        outcome = __atomic_load_n((int *) hs, __ATOMIC_ACQUIRE);
+        if (outcome == kWaitMatched || test) break;
+        if (used + a.timeout_ticks >= total_ticks) break;  // kWaitTimedOut: the whole bound has passed
+        if (sync_is_all(mode)) {
+            // Progress travels to the next slice: what was seen satisfied is not read again.
+            a.start = line[3];
+            for (int u = 0; u < kSyncUnroll; ++u) a.done_in[u] = line[4 + u];
+        }
+    }
+    bool found = hiperr.empty() && outcome == kWaitMatched;
+    if (found && sync_is_some(mode)) {
+        // The status word was seen, the kernel may still be ending: the indices (ordinary stores, which
+        // memory the caller does not map coherently may keep in the device's L2 until then) are read
+        // after its end.
+        const hipError_t e = hipStreamSynchronize(st);
+        if (e != hipSuccess) {
+            hiperr = hipGetErrorString(e);
+            found = false;
+        }
+    }
+    const uint64_t r = found || (test && hiperr.empty()) ? line[2] : sync_no_result(mode);
+    if (found && sync_is_some(mode) && user_indices) memcpy(user_indices, staged_indices, (size_t) r * sizeof(size_t));
+    std::lock_guard<std::mutex> lk(s.mu);
+    s.wait_busy[slot] = false;
+    if (!hiperr.empty()) return fail(what + ": " + hiperr);
+    if (result) *result = r;
+    if (outcome == kWaitTimedOut && !test) {
+        s.error_count++;
+        return fail(what + ": timed out after timeout_ms (" + std::to_string(s.timeout_ms) +
+                    " ms): the condition did not become true");
+    }
+    return 0;
+}
+
+int sync_vector_on_stream_impl(int mode_bits, int dt, void *ivars, size_t nelems, size_t *indices, const int *status, int cmp,
+                               uint64_t cmp_bits, const void *cmp_values, size_t *result, int *ret, hipStream_t st)
+{
+    State &s = S();
+    std::lock_guard<std::mutex> lk(s.mu);
+    const int mode = mode_bits & ~ISHMEMI_C_SYNC_VECTOR;
+    if (mode < 0 || mode >= kSyncModes || sync_is_test(mode)) {
+        if (!s.initialized) return fail("sync_vector_on_stream: not initialized");
+        return fail("sync_vector_on_stream: mode " + std::to_string(mode_bits) +
+                    " is not ISHMEMI_C_SYNC_WAIT_ALL, _WAIT_ANY or _WAIT_SOME (the tests have no on-stream form)");
+    }
+    const std::string what = std::string(kSyncName[mode]) + "_on_stream";
+    SyncVecArgs a{};
+    if (sync_vector_args(s, what, mode_bits, dt, ivars, nelems, indices, cmp, cmp_bits, cmp_values, a)) return 1;
+    // The arrays are read when the kernel runs (at every replay of a captured graph): they must be
+    // memory the device can address.
+    const void *user[5] = {status, cmp_values, sync_is_some(mode) ? indices : nullptr, result, ret};
+    const char *const name[5] = {"status", "cmp_values", "indices", "result", "ret"};
+    char *view[5] = {};
+    for (int k = 0; k < 5; ++k)
+        if (user[k] && (k >= 3 || nelems) && !(view[k] = device_view(s, user[k])))
+            return fail(what + ": " + name[k] + " is not device-accessible (heap, device or pinned host memory; pageable "
+                        "host memory is accepted by the blocking host forms only)");
+    if (wait_lines(s)) return 1;
+    a.status = (const int *) view[0];
+    a.cmp_values = view[1];
+    a.indices = (size_t *) view[2];
+    a.result_out = (uint64_t *) view[3];
+    a.status_out = (int *) view[4];
+    a.rotor = (uint64_t *) (s.wait_dev + (size_t) (kWaitSlots + 1) * 64);
+    a.timeout_ticks = (uint64_t) s.timeout_ms * 100000ull;
+    a.err = s.err_dev + kMaxTeams;
+    // As wait_until_on_stream: not ordered against other streams' calls; every pointer is a frozen
+    // kernel argument, so the call can be captured into a graph.
+    HIP_TRY(launch_sync_vector(a, st));
     return 0;
 }
 
@@ -2243,6 +2479,7 @@ int sync_device_ctx(State &s)
     c.epochs = s.dev_epochs;
     c.dev_counts = (uint64_t *) (s.count_slots + (size_t) kMaxTeams * 64);
     c.err = s.err_dev + kMaxTeams;
+    c.sync_rotor = (uint64_t *) (s.dev_epochs + kMaxTeams);
     for (int t = 0; t < kMaxTeams; ++t) {
         const Team &tm = s.teams[t];
         c.team_start[t] = tm.start;
@@ -2715,9 +2952,13 @@ int init_impl(int pe, int npes, int device, const std::string &key)
         HIP_TRY(hipMalloc((void **) &s.kern_ep, ep_bytes));
     }
     HIP_TRY(hipMemset(s.kern_ep, 0, ep_bytes));
-    HIP_TRY(hipMalloc((void **) &s.dev_epochs, kMaxTeams * sizeof(uint32_t)));
-    HIP_TRY(hipMemset(s.dev_epochs, 0, kMaxTeams * sizeof(uint32_t)));
+    // ... and, behind the epochs, the line of the device calls' wait_until_any / test_any rotor.
+    HIP_TRY(hipMalloc((void **) &s.dev_epochs, kMaxTeams * sizeof(uint32_t) + 64));
+    HIP_TRY(hipMemset(s.dev_epochs, 0, kMaxTeams * sizeof(uint32_t) + 64));
     if (sync_device_ctx(s)) return 1;
+    // The wait lines now: an on-stream vector wait points its kernel at the rotor among them and must
+    // not allocate while a stream capture is open.
+    if (wait_lines(s)) return 1;
     HIP_TRY(hipDeviceSynchronize());
     phase_done(6);
     s.init_us[7] = std::chrono::duration<double, std::micro>(clk::now() - t_start).count();
@@ -3021,6 +3262,9 @@ int ishmemi_c_finalize(void)
         if (s.wait_stream[k]) (void) hipStreamDestroy(s.wait_stream[k]);
         s.wait_stream[k] = nullptr;
         s.wait_busy[k] = false;
+        if (s.sync_stage_host[k]) (void) hipHostFree(s.sync_stage_host[k]);
+        s.sync_stage_host[k] = s.sync_stage_dev[k] = nullptr;
+        s.sync_stage_bytes[k] = 0;
     }
     if (s.wait_host) (void) hipHostFree(s.wait_host);
     s.wait_host = s.wait_dev = nullptr;
@@ -3665,6 +3909,23 @@ int ishmemi_c_wait_until_on_stream(void *ivar, int dtype, int cmp, uint64_t cmp_
                                    void *stream)
 {
     return wait_until_on_stream_impl(ivar, dtype, cmp, cmp_value_bits, value, ret, (hipStream_t) stream);
+}
+
+int ishmemi_c_sync_vector(int mode, int dtype, void *ivars, size_t nelems, size_t *indices, const int *status, int cmp,
+                          uint64_t cmp_value_bits, const void *cmp_values, size_t *result)
+{
+    uint64_t r = 0;
+    const int rc = host_sync_vector(mode, dtype, ivars, nelems, indices, status, cmp, cmp_value_bits, cmp_values, &r);
+    if (result) *result = (size_t) r;
+    return rc;
+}
+
+int ishmemi_c_sync_vector_on_stream(int mode, int dtype, void *ivars, size_t nelems, size_t *indices, const int *status,
+                                    int cmp, uint64_t cmp_value_bits, const void *cmp_values, size_t *result, int *ret,
+                                    void *stream)
+{
+    return sync_vector_on_stream_impl(mode, dtype, ivars, nelems, indices, status, cmp, cmp_value_bits, cmp_values, result,
+                                      ret, (hipStream_t) stream);
 }
 
 int ishmemi_c_resync(void)
