@@ -26,6 +26,7 @@
 #include "ishmem_amo.h"
 #include "ishmem_capi.h"
 #include "ishmem_sync.h"
+#include "ishmemx_fp16.h"
 
 /* ---- version, threading (src/ishmem.h:17-26) ---------------------------------------------- */
 #define ISHMEM_MAJOR_VERSION ISHMEMI_C_SPEC_MAJOR
@@ -137,7 +138,7 @@ inline int ishmem_team_sync(ishmem_team_t team) { return ishmemi_c_team_sync(tea
 namespace ishmemi_cxx {
 /* C type -> canonical dtype (the reference's ishmemi_union_get_base_type, src/ishmem/util.h:452-479) */
 template <typename T>
-constexpr int dtype_of()
+constexpr int dtype_of_base()
 {
     static_assert(std::is_arithmetic_v<T> && sizeof(T) <= 8, "unsupported reduction type");
     if constexpr (std::is_same_v<T, float>) return ISHMEMI_DT_FLOAT;
@@ -148,6 +149,14 @@ constexpr int dtype_of()
     else
         return sizeof(T) == 1 ? ISHMEMI_DT_UINT8 : sizeof(T) == 2 ? ISHMEMI_DT_UINT16
                : sizeof(T) == 4 ? ISHMEMI_DT_UINT32 : ISHMEMI_DT_UINT64;
+}
+/* ... and the 16-bit floating-point extension types (ishmemx_fp16.h), for reductions only. */
+template <typename T>
+constexpr int dtype_of()
+{
+    if constexpr (fp16_kind<T>() == 1) return ISHMEMI_DT_HALF;
+    else if constexpr (fp16_kind<T>() == 2) return ISHMEMI_DT_BFLOAT16;
+    else return dtype_of_base<T>();
 }
 template <typename T>
 inline int reduce(ishmem_team_t team, int op, T *dest, const T *source, size_t nreduce)

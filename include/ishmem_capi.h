@@ -48,7 +48,12 @@ typedef enum {
     ISHMEMI_DT_UINT64 = 7,
     ISHMEMI_DT_FLOAT = 8,
     ISHMEMI_DT_DOUBLE = 9,
-    ISHMEMI_DT_COUNT = 10
+    ISHMEMI_DT_COUNT = 10, /* the reference's types: ids 0 .. 9 */
+    /* Extension: 16-bit floating point, for reductions only (reduce, reduce_on_stream[_deps] and
+     * combine with max / min / sum / prod).  Every other entry that takes a dtype
+     * (scans, AMOs, waits, tests, vector waits) refuses them.  Ids 10 .. 15 are not types. */
+    ISHMEMI_DT_HALF = 16,    /* IEEE binary16 */
+    ISHMEMI_DT_BFLOAT16 = 17 /* bfloat16 */
 } ishmemi_c_dtype_t;
 
 /* Team handles — src/ishmem.h:61-72 (ISHMEM_TEAM_WORLD 0, ISHMEM_TEAM_SHARED 1) and
@@ -508,7 +513,9 @@ long long ishmemi_c_get_param(const char *name);
 int ishmemi_c_phase_times(float *ms5);
 /* Number of collective launches whose device-side barriers timed out since init. */
 int ishmemi_c_error_count(void);
-/* Bytes of one element of `dtype` (0 if invalid); 1 if (op, dtype) is a valid pair. */
+/* Bytes of one element of `dtype` (0 if invalid: ids 10 .. 15 and from 18 up included; 2 for
+ * ISHMEMI_DT_HALF / BFLOAT16); 1 if (op, dtype) is a valid pair of a reduction (the 16-bit types:
+ * max / min / sum / prod, like float). */
 size_t ishmemi_c_dtype_size(int dtype);
 int ishmemi_c_op_dtype_valid(int op, int dtype);
 /* Partition used by the multi-PE schedule: items of member `c` out of `nitems` (test hook). */

@@ -117,6 +117,39 @@ ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_ON_STREAM, min, ISHMEMI_OP_MIN)
 ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_ON_STREAM, sum, ISHMEMI_OP_SUM)
 ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_ON_STREAM, prod, ISHMEMI_OP_PROD)
 
+/* Extension (no reference counterpart): reductions of IEEE binary16 ("half") and bfloat16 arrays,
+ *   int ishmemx_{half,bfloat16}_{max,min,sum,prod}_reduce([team,] dest, source, nreduce)
+ *   int ishmemx_{half,bfloat16}_{max,min,sum,prod}_reduce_on_stream([team,] dest, source, nreduce,
+ *                                                                   ret, stream[, deps, ndeps, done])
+ * on ishmemx_half_t / ishmemx_bfloat16_t (ishmem.h).  Per element the result is the team-order
+ * fold acc = x_0; acc = round_to_nearest_even_T(f32(acc) OP f32(x_j)), rounded after every step
+ * (DESIGN.md §3g).  The generic ishmem_<op>_reduce<T> / ishmemx_<op>_reduce_on_stream<T> take the
+ * same two types and, under hipcc, _Float16, __half, __bf16 and __hip_bfloat16.  Not for scans,
+ * AMOs or waits: those refuse the types. */
+#define ISHMEMI_CXX_FP16_BLOCKING(TYPENAME, TYPE, OPNAME, OPC)                                      \
+    inline int ishmemx_##TYPENAME##_##OPNAME##_reduce(TYPE *dest, const TYPE *source,              \
+                                                      size_t nreduce)                              \
+    {                                                                                              \
+        return ishmemi_cxx::reduce<TYPE>(ISHMEM_TEAM_WORLD, OPC, dest, source, nreduce);           \
+    }                                                                                              \
+    inline int ishmemx_##TYPENAME##_##OPNAME##_reduce(ishmem_team_t team, TYPE *dest,              \
+                                                      const TYPE *source, size_t nreduce)          \
+    {                                                                                              \
+        return ishmemi_cxx::reduce<TYPE>(team, OPC, dest, source, nreduce);                        \
+    }
+#define ISHMEMI_CXX_FP16_TYPES(X, OPNAME, OPC)                                                      \
+    X(half, ishmemx_half_t, OPNAME, OPC)                                                           \
+    X(bfloat16, ishmemx_bfloat16_t, OPNAME, OPC)
+
+ISHMEMI_CXX_FP16_TYPES(ISHMEMI_CXX_FP16_BLOCKING, max, ISHMEMI_OP_MAX)
+ISHMEMI_CXX_FP16_TYPES(ISHMEMI_CXX_FP16_BLOCKING, min, ISHMEMI_OP_MIN)
+ISHMEMI_CXX_FP16_TYPES(ISHMEMI_CXX_FP16_BLOCKING, sum, ISHMEMI_OP_SUM)
+ISHMEMI_CXX_FP16_TYPES(ISHMEMI_CXX_FP16_BLOCKING, prod, ISHMEMI_OP_PROD)
+ISHMEMI_CXX_FP16_TYPES(ISHMEMI_CXX_ON_STREAM, max, ISHMEMI_OP_MAX)
+ISHMEMI_CXX_FP16_TYPES(ISHMEMI_CXX_ON_STREAM, min, ISHMEMI_OP_MIN)
+ISHMEMI_CXX_FP16_TYPES(ISHMEMI_CXX_ON_STREAM, sum, ISHMEMI_OP_SUM)
+ISHMEMI_CXX_FP16_TYPES(ISHMEMI_CXX_ON_STREAM, prod, ISHMEMI_OP_PROD)
+
 /* fcollect / collect / scan on a stream (src/ishmemx.h fcollect/collect/inscan/exscan _on_queue). */
 inline int ishmemx_fcollectmem_on_stream(ishmem_team_t team, void *dest, const void *source,
                                          size_t nbytes, int *ret, hipStream_t stream)

@@ -52,6 +52,7 @@
 #include "ishmem_amo.h"
 #include "ishmem_capi.h"
 #include "ishmem_sync.h"
+#include "ishmemx_fp16.h"
 
 namespace ishmemx_dev {
 
@@ -61,11 +62,36 @@ static __device__ const ishmemi_c_device_ctx_t *g_ctx = nullptr;
 
 __device__ __forceinline__ const ishmemi_c_device_ctx_t *ctx() { return g_ctx; }
 
+// The 16-bit floating-point types (ishmemx_fp16.h): round_to_nearest_even_T(f32(a) OP f32(b)) on
+// the type's bits, the host kernels' fold — plain casts, no hand-written conversion.
+template <typename T, int OP>
+__device__ __forceinline__ T op1_fp16(T a, T b)
+{
+    static_assert(sizeof(T) == 2 && OP >= ISHMEMI_OP_MAX, "16-bit floating point: max, min, sum and prod only");
+    constexpr bool half = ishmemi_cxx::fp16_kind<T>() == 1;
+    const uint16_t ab = __builtin_bit_cast(uint16_t, a), bb = __builtin_bit_cast(uint16_t, b);
+    float x, y, r;
+    if constexpr (half) {
+        x = (float) __builtin_bit_cast(_Float16, ab);
+        y = (float) __builtin_bit_cast(_Float16, bb);
+    } else {
+        x = (float) __builtin_bit_cast(__bf16, ab);
+        y = (float) __builtin_bit_cast(__bf16, bb);
+    }
+    if constexpr (OP == ISHMEMI_OP_MAX) r = fmaxf(x, y);
+    else if constexpr (OP == ISHMEMI_OP_MIN) r = fminf(x, y);
+    else if constexpr (OP == ISHMEMI_OP_SUM) r = x + y;
+    else r = x * y;
+    if constexpr (half) return __builtin_bit_cast(T, __builtin_bit_cast(uint16_t, (_Float16) r));
+    else return __builtin_bit_cast(T, __builtin_bit_cast(uint16_t, (__bf16) r));
+}
+
 template <typename T, int OP>
 __device__ __forceinline__ T op1(T a, T b)
 {
     using W = std::conditional_t<(sizeof(T) == 8), uint64_t, uint32_t>;
-    if constexpr (OP == ISHMEMI_OP_AND) return (T) (a & b);
+    if constexpr (ishmemi_cxx::fp16_kind<T>() != 0) return op1_fp16<T, OP>(a, b);
+    else if constexpr (OP == ISHMEMI_OP_AND) return (T) (a & b);
     else if constexpr (OP == ISHMEMI_OP_OR) return (T) (a | b);
     else if constexpr (OP == ISHMEMI_OP_XOR) return (T) (a ^ b);
     else if constexpr (OP == ISHMEMI_OP_MAX) {
@@ -1491,6 +1517,41 @@ ISHMEMX_DEV_ARITH_TYPES(ISHMEMX_DEV_TYPED, min, ISHMEMI_OP_MIN)
 ISHMEMX_DEV_ARITH_TYPES(ISHMEMX_DEV_TYPED, sum, ISHMEMI_OP_SUM)
 ISHMEMX_DEV_ARITH_TYPES(ISHMEMX_DEV_TYPED, prod, ISHMEMI_OP_PROD)
 ISHMEMX_DEV_ARITH_TYPES(ISHMEMX_DEV_COLL, _, _)
+
+/* Extension (no reference counterpart): the 16-bit floating-point reductions from a kernel,
+ *   ishmemx_{half,bfloat16}_{max,min,sum,prod}_reduce_work_group([team,] dest, source, nreduce, grp)
+ *   ishmemx_{half,bfloat16}_{max,min,sum,prod}_reduce([team,] dest, source, nreduce)   (one work-item)
+ * on ishmemx_half_t / ishmemx_bfloat16_t; the generic forms above also take _Float16, __half,
+ * __bf16 and __hip_bfloat16.  Same team-order, round-every-step fold as the host path. */
+#define ISHMEMX_DEV_FP16_TYPED(TYPENAME, TYPE, OPNAME, OPC)                                         \
+    template <typename Group>                                                                      \
+    __device__ inline int ishmemx_##TYPENAME##_##OPNAME##_reduce_work_group(                       \
+        TYPE *dest, const TYPE *source, size_t nreduce, const Group &grp)                          \
+    {                                                                                              \
+        return ishmemx_##OPNAME##_reduce_work_group<TYPE>(dest, source, nreduce, grp);             \
+    }                                                                                              \
+    template <typename Group>                                                                      \
+    __device__ inline int ishmemx_##TYPENAME##_##OPNAME##_reduce_work_group(                       \
+        int team, TYPE *dest, const TYPE *source, size_t nreduce, const Group &grp)                \
+    {                                                                                              \
+        return ishmemx_##OPNAME##_reduce_work_group<TYPE>(team, dest, source, nreduce, grp);       \
+    }                                                                                              \
+    __device__ inline int ishmemx_##TYPENAME##_##OPNAME##_reduce(TYPE *dest, const TYPE *source,   \
+                                                                 size_t nreduce)                   \
+    {                                                                                              \
+        return ishmem_##OPNAME##_reduce<TYPE>(dest, source, nreduce);                              \
+    }                                                                                              \
+    __device__ inline int ishmemx_##TYPENAME##_##OPNAME##_reduce(int team, TYPE *dest,             \
+                                                                 const TYPE *source, size_t nreduce) \
+    {                                                                                              \
+        return ishmem_##OPNAME##_reduce<TYPE>(team, dest, source, nreduce);                        \
+    }
+#define ISHMEMX_DEV_FP16_TYPES(X, OPNAME, OPC)                                                      \
+    X(half, ishmemx_half_t, OPNAME, OPC) X(bfloat16, ishmemx_bfloat16_t, OPNAME, OPC)
+ISHMEMX_DEV_FP16_TYPES(ISHMEMX_DEV_FP16_TYPED, max, ISHMEMI_OP_MAX)
+ISHMEMX_DEV_FP16_TYPES(ISHMEMX_DEV_FP16_TYPED, min, ISHMEMI_OP_MIN)
+ISHMEMX_DEV_FP16_TYPES(ISHMEMX_DEV_FP16_TYPED, sum, ISHMEMI_OP_SUM)
+ISHMEMX_DEV_FP16_TYPES(ISHMEMX_DEV_FP16_TYPED, prod, ISHMEMI_OP_PROD)
 
 /* ---- put / get / p / g, quiet / fence from a kernel (src/ishmem.h:90-330, src/ishmemx.h) --------
  * ishmem_<TN>_put / _get (one work-item; every calling work-item moves its own arguments),

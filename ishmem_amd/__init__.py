@@ -22,7 +22,9 @@ _L = load()
 # ---- enums (include/ishmem_capi.h) -------------------------------------------------------
 OPS = {"and": 0, "or": 1, "xor": 2, "max": 3, "min": 4, "sum": 5, "prod": 6}
 DTYPES = {"int8": 0, "int16": 1, "int32": 2, "int64": 3, "uint8": 4, "uint16": 5,
-          "uint32": 6, "uint64": 7, "float": 8, "double": 9}
+          "uint32": 6, "uint64": 7, "float": 8, "double": 9,
+          # Extension: 16-bit floating point, for reduce / reduce_on_stream / combine only.
+          "half": 16, "bfloat16": 17}
 ISHMEM_TEAM_INVALID = -1
 ISHMEM_TEAM_WORLD = 0
 ISHMEM_TEAM_SHARED = 1
@@ -801,3 +803,23 @@ for _op, _tns in TYPENAMES_FOR_OP.items():
         setattr(_mod, _xname, _g)
         API_NAMES += [_name, _xname]
 del _op, _tns, _tn, _name, _f, _xname, _g
+
+# ---- 16-bit floating-point reductions (extension, no reference counterpart) ----------
+# ishmemx_{half,bfloat16}_{max,min,sum,prod}_reduce([team,] dest, source, nreduce) and
+# ..._reduce_on_stream([team,] dest, source, nreduce, ret, stream); buffers hold the types' 16-bit
+# encodings.  reduce / reduce_on_stream / combine take the dtype names "half" and "bfloat16".
+HALF_TYPENAMES = ["half", "bfloat16"]
+HALF_NAMES: list[str] = []
+for _tn in HALF_TYPENAMES:
+    for _op in ("max", "min", "sum", "prod"):
+        _name = f"ishmemx_{_tn}_{_op}_reduce"
+        _f = _make_blocking(_op, _tn)
+        _f.__name__ = _name
+        _f.__doc__ = f"{_name}([team,] dest, source, nreduce) -> int"
+        setattr(_mod, _name, _f)
+        _xname = f"{_name}_on_stream"
+        _g = _make_on_stream(_op, _tn)
+        _g.__name__ = _xname
+        setattr(_mod, _xname, _g)
+        HALF_NAMES += [_name, _xname]
+del _tn, _op, _name, _f, _xname, _g

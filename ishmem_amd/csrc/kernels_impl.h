@@ -73,11 +73,55 @@ struct WideOf<uint64_t> {
     using type = uint64_t;
 };
 
+// The 16-bit floating-point element types (ISHMEMI_DT_HALF / ISHMEMI_DT_BFLOAT16): storage only,
+// so every Vec<T>, load and store site treats them like any other 2-byte element.  Their fold is
+// rn_T(f32(a) OP f32(b)): exact widening, the IEEE f32 operation, one rounding to
+// nearest even back to the type after every step — plain casts, which the compiler turns into
+// v_pk_add_f16 / v_pk_mul_f16 / v_pk_max_f16 for half (the f16 operation is the correctly rounded
+// f32 one) and into v_pk_add_f32 + v_cvt_pk_bf16_f32 for bfloat16.
+struct f16_t {
+    uint16_t b;
+};
+struct bf16_t {
+    uint16_t b;
+};
+template <typename T>
+inline constexpr bool is_fp16_v = std::is_same_v<T, f16_t> || std::is_same_v<T, bf16_t>;
+// Floating point in the sense of the fold order: sum / prod depend on it.
+template <typename T>
+inline constexpr bool is_fp_v = std::is_floating_point_v<T> || is_fp16_v<T>;
+
+template <typename T>
+__device__ __forceinline__ float widen16(T a)
+{
+    if constexpr (std::is_same_v<T, f16_t>) return (float) __builtin_bit_cast(_Float16, a.b);
+    else return (float) __builtin_bit_cast(__bf16, a.b);
+}
+
+template <typename T>
+__device__ __forceinline__ T narrow16(float f)
+{
+    if constexpr (std::is_same_v<T, f16_t>) return T{__builtin_bit_cast(uint16_t, (_Float16) f)};
+    else return T{__builtin_bit_cast(uint16_t, (__bf16) f)};
+}
+
+template <typename T, int OP>
+__device__ __forceinline__ T op1_fp16(T a, T b)
+{
+    static_assert(OP >= ISHMEMI_OP_MAX, "16-bit floating point: max, min, sum and prod only");
+    const float x = widen16(a), y = widen16(b);
+    if constexpr (OP == ISHMEMI_OP_MAX) return narrow16<T>(fmaxf(x, y));
+    else if constexpr (OP == ISHMEMI_OP_MIN) return narrow16<T>(fminf(x, y));
+    else if constexpr (OP == ISHMEMI_OP_SUM) return narrow16<T>(x + y);
+    else return narrow16<T>(x * y);
+}
+
 // reduce_op semantics of src/collectives/reduce_impl.h:83-102 on canonical types.
 template <typename T, int OP>
 __device__ __forceinline__ T op1(T a, T b)
 {
-    if constexpr (OP == ISHMEMI_OP_AND) return (T) (a & b);
+    if constexpr (is_fp16_v<T>) return op1_fp16<T, OP>(a, b);
+    else if constexpr (OP == ISHMEMI_OP_AND) return (T) (a & b);
     else if constexpr (OP == ISHMEMI_OP_OR) return (T) (a | b);
     else if constexpr (OP == ISHMEMI_OP_XOR) return (T) (a ^ b);
     else if constexpr (OP == ISHMEMI_OP_MAX) {
@@ -153,6 +197,7 @@ template <typename I>
 __device__ __forceinline__ void nt_store(I *p, const I &v)
 {
     if constexpr (sizeof(I) == 16) __builtin_nontemporal_store(__builtin_bit_cast(u32x4, v), (u32x4 *) p);
+    else if constexpr (is_fp16_v<I>) __builtin_nontemporal_store(v.b, (uint16_t *) p);
     else __builtin_nontemporal_store(v, p);
 }
 
@@ -553,7 +598,7 @@ __device__ __forceinline__ void rs_tile_any(const ReduceArgs &a, int rot, uint64
     using Item = std::conditional_t<VEC, Vec<T>, T>;
     constexpr uint64_t IB = sizeof(Item);
     constexpr bool kOrderFree =
-        !(std::is_floating_point_v<T> && (OP == ISHMEMI_OP_SUM || OP == ISHMEMI_OP_PROD));
+        !(is_fp_v<T> && (OP == ISHMEMI_OP_SUM || OP == ISHMEMI_OP_PROD));
     const uint32_t tid = threadIdx.x;
     const int p = a.p;
     const uint32_t lim = (uint32_t) min<uint64_t>(ce - t0, kTile);
@@ -918,6 +963,7 @@ template <typename I>
 __device__ __forceinline__ I nt_load(const I *p)
 {
     if constexpr (sizeof(I) == 16) return __builtin_bit_cast(I, __builtin_nontemporal_load((const u32x4 *) p));
+    else if constexpr (is_fp16_v<I>) return I{__builtin_nontemporal_load((const uint16_t *) p)};
     else return __builtin_nontemporal_load(p);
 }
 
@@ -1639,6 +1685,12 @@ hipError_t dispatch_dt(int dt, L &&launch)
             else return hipErrorInvalidValue;
         case ISHMEMI_DT_DOUBLE:
             if constexpr (fp_ok) return launch.template operator()<double, OP>();
+            else return hipErrorInvalidValue;
+        case ISHMEMI_DT_HALF:
+            if constexpr (fp_ok) return launch.template operator()<f16_t, OP>();
+            else return hipErrorInvalidValue;
+        case ISHMEMI_DT_BFLOAT16:
+            if constexpr (fp_ok) return launch.template operator()<bf16_t, OP>();
             else return hipErrorInvalidValue;
         default: return hipErrorInvalidValue;
     }

@@ -2351,7 +2351,7 @@ int scan_impl(int team, int dt, int inclusive, void *dst, const void *src, size_
     State &s = S();
     std::lock_guard<std::mutex> lk(s.mu);
     // The dtype is checked between team_call's two tests, as ever: "not initialized" comes first.
-    if (s.initialized && !op_dtype_valid(ISHMEMI_OP_SUM, dt)) return fail("scan: invalid dtype");
+    if (s.initialized && !scan_dtype_valid(dt)) return fail("scan: invalid dtype");
     if (team_call(s, "scan", team)) return 1;
     Team &t = s.teams[team];
     const size_t es = dtype_size(dt);
@@ -4167,7 +4167,7 @@ int ishmemi_c_scan(int team, int dtype, int inclusive, void *dest, const void *s
     // the reference (src/teams.h:29-38).
     State &s = S();
     const size_t bytes = nelems * dtype_size(dtype);
-    if (!member_call(s, team) || nelems == 0 || s.teams[team].size == 1 || !op_dtype_valid(ISHMEMI_OP_SUM, dtype))
+    if (!member_call(s, team) || nelems == 0 || s.teams[team].size == 1 || !scan_dtype_valid(dtype))
         return scan_impl(team, dtype, inclusive, dest, source, nelems, nullptr, 0, true);
     const uint64_t mine = (in_heap(s, source) && in_heap(s, dest)) ? 0 : kAgreeStaged;
     uint64_t any = 0;
@@ -4424,7 +4424,7 @@ int ishmemi_c_error_count(void)
 
 size_t ishmemi_c_dtype_size(int dtype)
 {
-    return (dtype >= 0 && dtype < ISHMEMI_DT_COUNT) ? dtype_size(dtype) : 0;
+    return dtype_known(dtype) ? dtype_size(dtype) : 0;
 }
 
 int ishmemi_c_op_dtype_valid(int op, int dtype) { return op_dtype_valid(op, dtype) ? 1 : 0; }

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Size sweep of the reduce path (dev tool): f32 sum (or --op/--dtype) over TEAM_WORLD for sizes
-4 B .. --max-mib, one process per PE (launch with torch.distributed.run for N>1; set
+"""Size sweep of the reduce path (dev tool): a sum of --dtype (float, half, bfloat16) over TEAM_WORLD,
+or the local 2-source combine (--coll combine), for sizes 4 B .. --max-mib, one process per PE (launch with torch.distributed.run for N>1; set
 ISHMEM_BENCH_SAME_DEVICE=1 to put every PE on device 0).  Prints one CSV row per size on rank 0:
 bytes, us per call (max over ranks), algbw GiB/s.  Results are checked against the closed form."""
 from __future__ import annotations
@@ -24,7 +24,10 @@ def main() -> None:
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--min-bytes", type=int, default=4)
     ap.add_argument("--factor", type=int, default=4)
-    ap.add_argument("--coll", choices=["reduce", "fcollect", "inscan", "broadcast"], default="reduce")
+    ap.add_argument("--coll", choices=["reduce", "fcollect", "inscan", "broadcast", "combine"], default="reduce",
+                    help="combine: dst = a + b of two local sources (the fan-in kernel), no team involved")
+    ap.add_argument("--dtype", choices=["float", "half", "bfloat16"], default="float",
+                    help="element type of reduce / combine (the 16-bit types: DESIGN.md 3g); sizes stay in bytes")
     ap.add_argument("--graph", action="store_true", help="time a hipGraph of --iters captured calls")
     ap.add_argument("--blocking", action="store_true",
                     help="blocking host calls (ishmem_fcollectmem / ishmem_float_sum_inscan / ishmem_float_sum_reduce), "
@@ -70,14 +73,31 @@ def main() -> None:
     for kv in args.param:
         name, val = kv.split("=", 1)
         ish.set_param(name, int(val))
-    nmax = (args.max_mib << 20) // 4
-    so, do = args.src_offset // 4, args.dst_offset // 4
-    src = ish.ishmem_malloc(nmax * 4 + 64)
-    dst = ish.ishmem_malloc(nmax * 4 * (world if args.coll == "fcollect" else 1) + 64)
-    hip.upload(src, (np.arange(nmax + 16, dtype=np.int64) % 1024).astype(np.float32) + np.float32(rank))
+    if args.dtype != "float" and args.coll not in ("reduce", "combine"):
+        raise SystemExit("--dtype half / bfloat16: reduce and combine only")
+    es = 4 if args.dtype == "float" else 2
+    # Values whose sums over 8 PEs are exact in the type: i mod 1024 for float, i mod 16 for the 16-bit types.
+    mod = 1024 if args.dtype == "float" else 16
+
+    def encode(x):  # float32 values the type holds exactly -> the type's storage
+        x = np.ascontiguousarray(x, dtype=np.float32)
+        if args.dtype == "float":
+            return x
+        return x.astype(np.float16).view(np.uint16) if args.dtype == "half" else (x.view(np.uint32) >> 16).astype(np.uint16)
+
+    nmax = (args.max_mib << 20) // es
+    so, do = args.src_offset // es, args.dst_offset // es
+    src = ish.ishmem_malloc(nmax * es + 64)
+    dst = ish.ishmem_malloc(nmax * es * (world if args.coll == "fcollect" else 1) + 64)
+    hip.upload(src, encode((np.arange(nmax + 16, dtype=np.int64 if nmax >= (1 << 31) - 16 else np.int32) % mod).astype(np.float32)
+                           + np.float32(rank)))
+    src2 = 0
+    if args.coll == "combine":
+        src2 = ish.ishmem_malloc(nmax * es + 64)
+        hip.memcpy(src2, src, nmax * es + 32)
     st = hip.stream_create()
     if rank == 0:
-        print(f"# coll={args.coll} graph={args.graph} blocking={args.blocking} pes={world} same_device={os.environ.get('ISHMEM_BENCH_SAME_DEVICE') == '1'} "
+        print(f"# coll={args.coll} dtype={args.dtype} graph={args.graph} blocking={args.blocking} pes={world} same_device={os.environ.get('ISHMEM_BENCH_SAME_DEVICE') == '1'} "
               f"ll_max_bytes={ish.get_param('ll_max_bytes')} wait_slots={ish.get_param('wait_slots')} "
               f"device_share={ish.get_param('device_share')} src_offset={args.src_offset} dst_offset={args.dst_offset} params={args.param}")
         print("bytes,us_per_call,algbw_GiBps,ok")
@@ -89,29 +109,37 @@ def main() -> None:
                 return ish.ishmem_broadcastmem(dst, src, n * 4, 0)
             if args.coll == "inscan":
                 return ish.lib().ishmemi_c_scan(0, ish.DTYPES["float"], 1, dst, src, n)
-            return ish.ishmem_float_sum_reduce(dst, src, n)
+            if args.coll == "combine":
+                rc = ish.combine("sum", args.dtype, dst + es * do, [src + es * so, src2 + es * so], n)
+                hip.synchronize()
+                return rc
+            return ish.reduce("sum", args.dtype, dst, src, n)
         if args.coll == "fcollect":
             return ish.fcollect_on_stream(dst, src, n * 4, 0, st)
         if args.coll == "broadcast":
             return ish.broadcast_on_stream(dst, src, n * 4, 0, 0, st)
         if args.coll == "inscan":
             return ish.lib().ishmemi_c_scan_on_stream(0, ish.DTYPES["float"], 1, dst, src, n, None, st)
+        if args.coll == "combine":
+            return ish.combine("sum", args.dtype, dst + es * do, [src + es * so, src2 + es * so], n, st)
         if args.inplace:
-            return ish.ishmemx_float_sum_reduce_on_stream(src + 4 * so, src + 4 * so, n, 0, st)
-        return ish.ishmemx_float_sum_reduce_on_stream(dst + 4 * do, src + 4 * so, n, 0, st)
+            return ish.reduce_on_stream("sum", args.dtype, src + es * so, src + es * so, n, 0, st)
+        return ish.reduce_on_stream("sum", args.dtype, dst + es * do, src + es * so, n, 0, st)
 
     def expect(i, n):
         i = i + so
-        base = (i % 1024).astype(np.float32)
+        base = (i % mod).astype(np.float32)
         if args.coll == "fcollect":  # the last k elements of the dest = PE world-1's tail
             return base + np.float32(world - 1)
         if args.coll == "broadcast":  # root 0's source
             return base
         if args.coll == "inscan":
             return base * (rank + 1) + np.float32(rank * (rank + 1) / 2)
-        return base * world + np.float32(world * (world - 1) / 2)
+        if args.coll == "combine":
+            return encode((base + np.float32(rank)) * 2)
+        return encode(base * world + np.float32(world * (world - 1) / 2))
 
-    n = max(1, args.min_bytes // 4)
+    n = max(1, args.min_bytes // es)
     while n <= nmax:
         for _ in range(3):
             call(n)
@@ -119,7 +147,7 @@ def main() -> None:
         if dist is not None:
             dist.barrier()
         e0, e1 = hip.Event(), hip.Event()
-        iters = args.iters if n < (1 << 24) else max(3, args.iters // 4)
+        iters = args.iters if n * es < (1 << 26) else max(3, args.iters // 4)
         if args.graph:
             with hip.Graph(st) as g:
                 for _ in range(iters):
@@ -153,10 +181,10 @@ def main() -> None:
             us = float(t[0])
         k = min(n, 64)
         last = n * (world if args.coll == "fcollect" else 1)
-        got = hip.download(dst + 4 * do + (last - k) * 4, k, np.float32)
+        got = hip.download(dst + es * do + (last - k) * es, k, np.float32 if es == 4 else np.uint16)
         ok = -1 if args.inplace else int(np.array_equal(got, expect(np.arange(n - k, n), n)))
         if rank == 0:
-            print(f"{n * 4},{us:.2f},{n * 4 / 2**30 / (us * 1e-6):.2f},{int(ok)}", flush=True)
+            print(f"{n * es},{us:.2f},{n * es / 2**30 / (us * 1e-6):.2f},{int(ok)}", flush=True)
         n *= args.factor
     if args.phases and args.coll == "reduce":
         n = n // args.factor
@@ -170,7 +198,7 @@ def main() -> None:
         r = ish.lib().ishmemi_c_phase_times(ms)
         ish.set_param("phase_events", 0)
         if rank == 0:
-            print(f"# phases bytes={n * 4} rc={r} " + " ".join(f"{k}={v:.4f}" for k, v in zip(
+            print(f"# phases bytes={n * es} rc={r} " + " ".join(f"{k}={v:.4f}" for k, v in zip(
                 ["start", "rs", "mid", "ag", "end"], list(ms))), flush=True)
     ish.ishmem_finalize()
 
