@@ -226,6 +226,24 @@ int ishmemi_c_fcollect_on_stream(int team, void *dest, const void *source, size_
 int ishmemi_c_alltoall(int team, void *dest, const void *source, size_t nbytes);
 int ishmemi_c_alltoall_on_stream(int team, void *dest, const void *source, size_t nbytes, int *ret,
                                  void *stream);
+/* reduce-scatter (extension, no reference counterpart; ishmemx_<TN>_<op>_reduce_scatter, DESIGN.md
+ * §3h): source holds p blocks of `nreduce` elements in the symmetric heap (alltoall's source layout);
+ * on member k (its index in the team) dest[i] = source_0[k*nreduce + i] OP ... OP
+ * source_{p-1}[k*nreduce + i], folded in team order — bit for bit elements [k*nreduce, (k+1)*nreduce)
+ * of what ishmemi_c_reduce over p*nreduce elements leaves in dest, for the (op, dtype) pairs of
+ * ishmemi_c_reduce (ISHMEMI_DT_HALF / _BFLOAT16 included).  dest: nreduce elements of device-writable
+ * memory (heap, device or pinned host; written by its owner only) that do not overlap the member's own
+ * p blocks.  On return (or when the stream work completes) dest is final and source may be rewritten.
+ * A team of one copies block 0; nreduce == 0 still synchronises the team.  The blocking call agrees on
+ * argument failures across the team before anything is launched (every member then fails); the
+ * stream-ordered calls check their own arguments and fail before any launch.  Argument order, *ret,
+ * deps and done as for the three ishmemi_c_reduce* calls. */
+int ishmemi_c_reduce_scatter(int team, int op, int dtype, void *dest, const void *source, size_t nreduce);
+int ishmemi_c_reduce_scatter_on_stream(int team, int op, int dtype, void *dest, const void *source,
+                                       size_t nreduce, int *ret, void *stream);
+int ishmemi_c_reduce_scatter_on_stream_deps(int team, int op, int dtype, void *dest, const void *source,
+                                            size_t nreduce, int *ret, void *stream, void *const *deps,
+                                            size_t ndeps, void *done);
 int ishmemi_c_collect(int team, void *dest, const void *source, size_t nbytes);
 /* collect enqueued on `stream` (ishmemx_<TN>_collect_on_queue, src/ishmemx.h): the members'
  * byte counts are exchanged on the device inside the launch, so the call returns at once.  *ret as

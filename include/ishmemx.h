@@ -150,6 +150,109 @@ ISHMEMI_CXX_FP16_TYPES(ISHMEMI_CXX_ON_STREAM, min, ISHMEMI_OP_MIN)
 ISHMEMI_CXX_FP16_TYPES(ISHMEMI_CXX_ON_STREAM, sum, ISHMEMI_OP_SUM)
 ISHMEMI_CXX_FP16_TYPES(ISHMEMI_CXX_ON_STREAM, prod, ISHMEMI_OP_PROD)
 
+/* Extension (no reference counterpart): reduce-scatter, the first half of what a large reduce does
+ * (DESIGN.md §3h),
+ *   int ishmemx_<TN>_<op>_reduce_scatter([team,] dest, source, nreduce)
+ *   int ishmemx_<TN>_<op>_reduce_scatter_on_stream([team,] dest, source, nreduce, ret, stream
+ *                                                  [, deps, ndeps, done])
+ * and the generic ishmemx_<op>_reduce_scatter<T> / ishmemx_<op>_reduce_scatter_on_stream<T>, for the
+ * (op, TYPENAME) pairs of ishmem_<TN>_<op>_reduce plus half and bfloat16 × max / min / sum / prod.
+ * source: p blocks of nreduce elements in the symmetric heap (alltoall's source layout).  On member k
+ * of a team of p, dest[i] = source_0[k*nreduce + i] OP ... OP source_{p-1}[k*nreduce + i], folded in
+ * team order: bit for bit elements [k*nreduce, (k+1)*nreduce) of what the reduce over p*nreduce
+ * elements leaves in dest.  dest: nreduce elements of heap, device or pinned host memory, not
+ * overlapping the member's own source.  On return (completion of the stream work) dest is final and
+ * source may be rewritten. */
+namespace ishmemi_cxx {
+template <typename T>
+inline int reduce_scatter(ishmem_team_t team, int op, T *dest, const T *source, size_t nreduce)
+{
+    return ishmemi_c_reduce_scatter(team, op, dtype_of<T>(), (void *) dest, (const void *) source, nreduce);
+}
+template <typename T>
+inline int reduce_scatter_on_stream(ishmem_team_t team, int op, T *dest, const T *source, size_t nreduce,
+                                    int *ret, hipStream_t stream)
+{
+    return ishmemi_c_reduce_scatter_on_stream(team, op, dtype_of<T>(), (void *) dest, (const void *) source,
+                                              nreduce, ret, (void *) stream);
+}
+template <typename T>
+inline int reduce_scatter_on_stream(ishmem_team_t team, int op, T *dest, const T *source, size_t nreduce,
+                                    int *ret, hipStream_t stream, const hipEvent_t *deps, size_t ndeps,
+                                    hipEvent_t done)
+{
+    return ishmemi_c_reduce_scatter_on_stream_deps(team, op, dtype_of<T>(), (void *) dest, (const void *) source,
+                                                   nreduce, ret, (void *) stream, (void *const *) deps, ndeps,
+                                                   (void *) done);
+}
+}  // namespace ishmemi_cxx
+
+#define ISHMEMI_CXX_RS_FORMS(TEMPLATE, PREFIX, TYPE, OPC)                                           \
+    TEMPLATE inline int PREFIX##_reduce_scatter(TYPE *dest, const TYPE *source, size_t nreduce)    \
+    {                                                                                              \
+        return ishmemi_cxx::reduce_scatter<TYPE>(ISHMEM_TEAM_WORLD, OPC, dest, source, nreduce);   \
+    }                                                                                              \
+    TEMPLATE inline int PREFIX##_reduce_scatter(ishmem_team_t team, TYPE *dest, const TYPE *source, \
+                                                size_t nreduce)                                    \
+    {                                                                                              \
+        return ishmemi_cxx::reduce_scatter<TYPE>(team, OPC, dest, source, nreduce);                \
+    }                                                                                              \
+    TEMPLATE inline int PREFIX##_reduce_scatter_on_stream(TYPE *dest, const TYPE *source,          \
+                                                          size_t nreduce, int *ret,                \
+                                                          hipStream_t stream)                      \
+    {                                                                                              \
+        return ishmemi_cxx::reduce_scatter_on_stream<TYPE>(ISHMEM_TEAM_WORLD, OPC, dest, source,   \
+                                                           nreduce, ret, stream);                  \
+    }                                                                                              \
+    TEMPLATE inline int PREFIX##_reduce_scatter_on_stream(ishmem_team_t team, TYPE *dest,          \
+                                                          const TYPE *source, size_t nreduce,      \
+                                                          int *ret, hipStream_t stream)            \
+    {                                                                                              \
+        return ishmemi_cxx::reduce_scatter_on_stream<TYPE>(team, OPC, dest, source, nreduce, ret,  \
+                                                           stream);                                \
+    }                                                                                              \
+    TEMPLATE inline int PREFIX##_reduce_scatter_on_stream(TYPE *dest, const TYPE *source,          \
+                                                          size_t nreduce, int *ret,                \
+                                                          hipStream_t stream,                      \
+                                                          const hipEvent_t *deps, size_t ndeps,    \
+                                                          hipEvent_t done)                         \
+    {                                                                                              \
+        return ishmemi_cxx::reduce_scatter_on_stream<TYPE>(ISHMEM_TEAM_WORLD, OPC, dest, source,   \
+                                                           nreduce, ret, stream, deps, ndeps,      \
+                                                           done);                                  \
+    }                                                                                              \
+    TEMPLATE inline int PREFIX##_reduce_scatter_on_stream(ishmem_team_t team, TYPE *dest,          \
+                                                          const TYPE *source, size_t nreduce,      \
+                                                          int *ret, hipStream_t stream,            \
+                                                          const hipEvent_t *deps, size_t ndeps,    \
+                                                          hipEvent_t done)                         \
+    {                                                                                              \
+        return ishmemi_cxx::reduce_scatter_on_stream<TYPE>(team, OPC, dest, source, nreduce, ret,  \
+                                                           stream, deps, ndeps, done);             \
+    }
+#define ISHMEMI_CXX_RS_GENERIC(OPNAME, OPC) ISHMEMI_CXX_RS_FORMS(template <typename T>, ishmemx_##OPNAME, T, OPC)
+#define ISHMEMI_CXX_RS_TYPED(TYPENAME, TYPE, OPNAME, OPC) \
+    ISHMEMI_CXX_RS_FORMS(, ishmemx_##TYPENAME##_##OPNAME, TYPE, OPC)
+
+ISHMEMI_CXX_RS_GENERIC(and, ISHMEMI_OP_AND)
+ISHMEMI_CXX_RS_GENERIC(or, ISHMEMI_OP_OR)
+ISHMEMI_CXX_RS_GENERIC(xor, ISHMEMI_OP_XOR)
+ISHMEMI_CXX_RS_GENERIC(max, ISHMEMI_OP_MAX)
+ISHMEMI_CXX_RS_GENERIC(min, ISHMEMI_OP_MIN)
+ISHMEMI_CXX_RS_GENERIC(sum, ISHMEMI_OP_SUM)
+ISHMEMI_CXX_RS_GENERIC(prod, ISHMEMI_OP_PROD)
+ISHMEMI_CXX_BITWISE_TYPES(ISHMEMI_CXX_RS_TYPED, and, ISHMEMI_OP_AND)
+ISHMEMI_CXX_BITWISE_TYPES(ISHMEMI_CXX_RS_TYPED, or, ISHMEMI_OP_OR)
+ISHMEMI_CXX_BITWISE_TYPES(ISHMEMI_CXX_RS_TYPED, xor, ISHMEMI_OP_XOR)
+ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_RS_TYPED, max, ISHMEMI_OP_MAX)
+ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_RS_TYPED, min, ISHMEMI_OP_MIN)
+ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_RS_TYPED, sum, ISHMEMI_OP_SUM)
+ISHMEMI_CXX_ARITH_TYPES(ISHMEMI_CXX_RS_TYPED, prod, ISHMEMI_OP_PROD)
+ISHMEMI_CXX_FP16_TYPES(ISHMEMI_CXX_RS_TYPED, max, ISHMEMI_OP_MAX)
+ISHMEMI_CXX_FP16_TYPES(ISHMEMI_CXX_RS_TYPED, min, ISHMEMI_OP_MIN)
+ISHMEMI_CXX_FP16_TYPES(ISHMEMI_CXX_RS_TYPED, sum, ISHMEMI_OP_SUM)
+ISHMEMI_CXX_FP16_TYPES(ISHMEMI_CXX_RS_TYPED, prod, ISHMEMI_OP_PROD)
+
 /* fcollect / collect / scan on a stream (src/ishmemx.h fcollect/collect/inscan/exscan _on_queue). */
 inline int ishmemx_fcollectmem_on_stream(ishmem_team_t team, void *dest, const void *source,
                                          size_t nbytes, int *ret, hipStream_t stream)

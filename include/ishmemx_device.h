@@ -392,6 +392,80 @@ __device__ int reduce_work_group(const ishmemi_c_device_ctx_t *c, int team, T *d
     return reduce_group<work_group_t, T, OP>(c, team, dest, source, nreduce);
 }
 
+// Reduce-scatter from inside a kernel (extension): source holds `size` blocks of
+// nreduce elements in the symmetric heap; this member folds block `me` of every member's source, in
+// team order, into dest (nreduce elements, written by this group only: any memory the kernel can
+// write).  reduce_group's start barrier (every source final), the fold — 16-B sys_load16 items,
+// member-batched as in reduce_group, when this member's block and dest are both 16-B aligned,
+// element-wise otherwise — and reduce_group's end barrier (no member returns while a peer may still
+// read its source); no middle barrier and no all-gather.  The epoch comes from c->epochs like the
+// siblings', so device reduces and reduce-scatters of one team may alternate.  dest overlapping
+// source is undefined.
+template <typename G, typename T, int OP>
+__device__ int reduce_scatter_group(const ishmemi_c_device_ctx_t *c, int team, T *dest, const T *source,
+                                    size_t nreduce)
+{
+    if (!c || team < 0 || team >= ISHMEMI_C_MAX_TEAMS) return 1;  // not initialised / bad handle
+    const int tid = G::rank(), nthr = G::size();
+    const int size = c->team_size[team], me = c->team_my_idx[team];
+    if (size <= 0 || me < 0) return 1;
+    uint32_t epoch = 0;
+    if (tid == 0)
+        epoch = __hip_atomic_fetch_add(c->epochs + team, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u;
+    epoch = G::bcast(epoch);
+    if (size == 1) {  // one PE: dest = block 0
+        if (dest != source)
+            for (size_t i = tid; i < nreduce; i += nthr) dest[i] = source[i];
+        G::sync();
+        return 0;
+    }
+    if (!group_barrier<G>(c, team, 0, epoch, true)) return 1;
+    const int start = c->team_start[team], stride = c->team_stride[team];
+    const T *block = source + (size_t) me * nreduce;  // the same offset in every member's heap
+    constexpr size_t E = 16 / sizeof(T);
+    const bool vec = ((((uintptr_t) dest) | ((uintptr_t) block)) & 15) == 0;
+    const size_t nv = vec ? nreduce / E : 0;
+    for (size_t v0 = 0; v0 < nv; v0 += (size_t) nthr * kUnroll) {
+        Vec16<T> acc[kUnroll];
+        for (int j0 = 0; j0 < size; j0 += kMemberBatch) {
+            Vec16<T> x[kMemberBatch][kUnroll];
+#pragma unroll
+            for (int b = 0; b < kMemberBatch; ++b) {
+                const int j = j0 + b;
+                if (j >= size) break;
+                const char *base = (j == me) ? (const char *) block : peer_addr(c, block, start + j * stride);
+                const char *step = group_uniform(base + v0 * 16);
+#pragma unroll
+                for (int u = 0; u < kUnroll; ++u) {
+                    const size_t k = (size_t) u * nthr + tid;
+                    if (v0 + k < nv) x[b][u] = sys_load16<T>(step, (uint32_t) (k * 16));
+                }
+            }
+#pragma unroll
+            for (int b = 0; b < kMemberBatch; ++b) {
+                if (j0 + b >= size) break;
+#pragma unroll
+                for (int u = 0; u < kUnroll; ++u) acc[u] = (j0 + b == 0) ? x[b][u] : op16<T, OP>(acc[u], x[b][u]);
+            }
+        }
+        char *dstep = (char *) group_uniform((const char *) dest + v0 * 16);
+#pragma unroll
+        for (int u = 0; u < kUnroll; ++u) {
+            const size_t k = (size_t) u * nthr + tid;
+            if (v0 + k < nv) sys_store16<T>(dstep, (uint32_t) (k * 16), acc[u]);
+        }
+    }
+    for (size_t i = nv * E + tid; i < nreduce; i += nthr) {
+        T acc = T();
+        for (int j = 0; j < size; ++j) {
+            const T x = (j == me) ? block[i] : sys_load((const T *) peer_addr(c, block + i, start + j * stride));
+            acc = (j == 0) ? x : op1<T, OP>(acc, x);
+        }
+        sys_store(dest + i, acc);
+    }
+    return group_barrier<G>(c, team, 2, epoch, false) ? 0 : 1;
+}
+
 // ---- fcollect / collect / sum-scan from inside a kernel ------------------------------------
 // The reference's ishmemx_<TN>_{fcollect,collect,sum_inscan,sum_exscan}_work_group and their
 // device-side blocking forms (src/ishmemx.h, src/collectives/collect_impl.h, scan_impl.h), on the
@@ -1277,6 +1351,76 @@ ISHMEMX_DEV_GENERIC(prod, ISHMEMI_OP_PROD)
         return ishmem_##OPNAME##_reduce<TYPE>(team, dest, source, nreduce);                        \
     }
 
+/* ---- reduce-scatter (extension; ishmemx.h has the semantics, DESIGN.md §3h the design) ---------
+ *   ishmemx_<TN>_<op>_reduce_scatter_work_group([team,] dest, source, nreduce, grp)
+ *   ishmemx_<TN>_<op>_reduce_scatter([team,] dest, source, nreduce)            (one work-item)
+ * and the generic ishmemx_<op>_reduce_scatter_work_group<T> / ishmemx_<op>_reduce_scatter<T>.
+ * dest overlapping source is undefined here (the host forms refuse it). */
+#define ISHMEMX_DEV_RS_GENERIC(OPNAME, OPC)                                                         \
+    template <typename T, typename Group>                                                          \
+    __device__ inline int ishmemx_##OPNAME##_reduce_scatter_work_group(T *dest, const T *source,   \
+                                                                       size_t nreduce, const Group &) \
+    {                                                                                              \
+        return ishmemx_dev::reduce_scatter_group<ishmemx_dev::exec_t<Group>, T, OPC>(              \
+            ishmemx_dev::ctx(), ISHMEMI_C_TEAM_WORLD, dest, source, nreduce);                      \
+    }                                                                                              \
+    template <typename T, typename Group>                                                          \
+    __device__ inline int ishmemx_##OPNAME##_reduce_scatter_work_group(int team, T *dest,          \
+                                                                       const T *source,            \
+                                                                       size_t nreduce, const Group &) \
+    {                                                                                              \
+        return ishmemx_dev::reduce_scatter_group<ishmemx_dev::exec_t<Group>, T, OPC>(              \
+            ishmemx_dev::ctx(), team, dest, source, nreduce);                                      \
+    }                                                                                              \
+    template <typename T>                                                                          \
+    __device__ inline int ishmemx_##OPNAME##_reduce_scatter(T *dest, const T *source, size_t nreduce) \
+    {                                                                                              \
+        return ishmemx_dev::reduce_scatter_group<ishmemx_dev::thread_t, T, OPC>(                   \
+            ishmemx_dev::ctx(), ISHMEMI_C_TEAM_WORLD, dest, source, nreduce);                      \
+    }                                                                                              \
+    template <typename T>                                                                          \
+    __device__ inline int ishmemx_##OPNAME##_reduce_scatter(int team, T *dest, const T *source,    \
+                                                            size_t nreduce)                        \
+    {                                                                                              \
+        return ishmemx_dev::reduce_scatter_group<ishmemx_dev::thread_t, T, OPC>(ishmemx_dev::ctx(), team, \
+                                                                                dest, source, nreduce); \
+    }
+
+ISHMEMX_DEV_RS_GENERIC(and, ISHMEMI_OP_AND)
+ISHMEMX_DEV_RS_GENERIC(or, ISHMEMI_OP_OR)
+ISHMEMX_DEV_RS_GENERIC(xor, ISHMEMI_OP_XOR)
+ISHMEMX_DEV_RS_GENERIC(max, ISHMEMI_OP_MAX)
+ISHMEMX_DEV_RS_GENERIC(min, ISHMEMI_OP_MIN)
+ISHMEMX_DEV_RS_GENERIC(sum, ISHMEMI_OP_SUM)
+ISHMEMX_DEV_RS_GENERIC(prod, ISHMEMI_OP_PROD)
+
+#define ISHMEMX_DEV_RS_TYPED(TYPENAME, TYPE, OPNAME, OPC)                                           \
+    template <typename Group>                                                                      \
+    __device__ inline int ishmemx_##TYPENAME##_##OPNAME##_reduce_scatter_work_group(               \
+        TYPE *dest, const TYPE *source, size_t nreduce, const Group &grp)                          \
+    {                                                                                              \
+        return ishmemx_##OPNAME##_reduce_scatter_work_group<TYPE>(dest, source, nreduce, grp);     \
+    }                                                                                              \
+    template <typename Group>                                                                      \
+    __device__ inline int ishmemx_##TYPENAME##_##OPNAME##_reduce_scatter_work_group(               \
+        int team, TYPE *dest, const TYPE *source, size_t nreduce, const Group &grp)                \
+    {                                                                                              \
+        return ishmemx_##OPNAME##_reduce_scatter_work_group<TYPE>(team, dest, source, nreduce, grp); \
+    }                                                                                              \
+    __device__ inline int ishmemx_##TYPENAME##_##OPNAME##_reduce_scatter(TYPE *dest, const TYPE *source, \
+                                                                         size_t nreduce)           \
+    {                                                                                              \
+        return ishmemx_dev::reduce_scatter_group<ishmemx_dev::thread_t, TYPE, OPC>(                \
+            ishmemx_dev::ctx(), ISHMEMI_C_TEAM_WORLD, dest, source, nreduce);                      \
+    }                                                                                              \
+    __device__ inline int ishmemx_##TYPENAME##_##OPNAME##_reduce_scatter(int team, TYPE *dest,     \
+                                                                         const TYPE *source,       \
+                                                                         size_t nreduce)           \
+    {                                                                                              \
+        return ishmemx_dev::reduce_scatter_group<ishmemx_dev::thread_t, TYPE, OPC>(ishmemx_dev::ctx(), team, \
+                                                                                   dest, source, nreduce); \
+    }
+
 /* ---- fcollect / collect / sum_inscan / sum_exscan / broadcast --------------------------------- */
 template <typename T, typename Group>
 __device__ inline int ishmemx_fcollect_work_group(int team, T *dest, const T *source, size_t nelems, const Group &)
@@ -1552,6 +1696,19 @@ ISHMEMX_DEV_FP16_TYPES(ISHMEMX_DEV_FP16_TYPED, max, ISHMEMI_OP_MAX)
 ISHMEMX_DEV_FP16_TYPES(ISHMEMX_DEV_FP16_TYPED, min, ISHMEMI_OP_MIN)
 ISHMEMX_DEV_FP16_TYPES(ISHMEMX_DEV_FP16_TYPED, sum, ISHMEMI_OP_SUM)
 ISHMEMX_DEV_FP16_TYPES(ISHMEMX_DEV_FP16_TYPED, prod, ISHMEMI_OP_PROD)
+
+/* The reduce-scatter extension's typed names: the reduce's matrix and the two 16-bit types. */
+ISHMEMX_DEV_BITWISE_TYPES(ISHMEMX_DEV_RS_TYPED, and, ISHMEMI_OP_AND)
+ISHMEMX_DEV_BITWISE_TYPES(ISHMEMX_DEV_RS_TYPED, or, ISHMEMI_OP_OR)
+ISHMEMX_DEV_BITWISE_TYPES(ISHMEMX_DEV_RS_TYPED, xor, ISHMEMI_OP_XOR)
+ISHMEMX_DEV_ARITH_TYPES(ISHMEMX_DEV_RS_TYPED, max, ISHMEMI_OP_MAX)
+ISHMEMX_DEV_ARITH_TYPES(ISHMEMX_DEV_RS_TYPED, min, ISHMEMI_OP_MIN)
+ISHMEMX_DEV_ARITH_TYPES(ISHMEMX_DEV_RS_TYPED, sum, ISHMEMI_OP_SUM)
+ISHMEMX_DEV_ARITH_TYPES(ISHMEMX_DEV_RS_TYPED, prod, ISHMEMI_OP_PROD)
+ISHMEMX_DEV_FP16_TYPES(ISHMEMX_DEV_RS_TYPED, max, ISHMEMI_OP_MAX)
+ISHMEMX_DEV_FP16_TYPES(ISHMEMX_DEV_RS_TYPED, min, ISHMEMI_OP_MIN)
+ISHMEMX_DEV_FP16_TYPES(ISHMEMX_DEV_RS_TYPED, sum, ISHMEMI_OP_SUM)
+ISHMEMX_DEV_FP16_TYPES(ISHMEMX_DEV_RS_TYPED, prod, ISHMEMI_OP_PROD)
 
 /* ---- put / get / p / g, quiet / fence from a kernel (src/ishmem.h:90-330, src/ishmemx.h) --------
  * ishmem_<TN>_put / _get (one work-item; every calling work-item moves its own arguments),

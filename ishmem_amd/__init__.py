@@ -823,3 +823,55 @@ for _tn in HALF_TYPENAMES:
         setattr(_mod, _xname, _g)
         HALF_NAMES += [_name, _xname]
 del _tn, _op, _name, _f, _xname, _g
+
+
+# ---- reduce-scatter (extension, no reference counterpart) ---------------------------
+# source: p blocks of nreduce elements in the symmetric heap (alltoall's source layout); member k's
+# dest (nreduce elements, any device-writable memory) = the team-order fold of every member's block k:
+# bit for bit elements [k * nreduce, (k + 1) * nreduce) of what reduce over p * nreduce elements gives.
+def reduce_scatter(op: str, dtype: str, dest: int, source: int, nreduce: int, team: int = ISHMEM_TEAM_WORLD) -> int:
+    return _L.ishmemi_c_reduce_scatter(team, OPS[op], DTYPES[dtype], dest, source, nreduce)
+
+
+def reduce_scatter_on_stream(op: str, dtype: str, dest: int, source: int, nreduce: int, ret: int | None,
+                             stream: int, team: int = ISHMEM_TEAM_WORLD, deps=(), done=None) -> int:
+    """Enqueued on `stream`; `ret`, `deps` and `done` as for reduce_on_stream."""
+    if deps or done is not None:
+        hs = [_event_handle(e) for e in deps]
+        arr = (ctypes.c_void_p * len(hs))(*hs) if hs else None
+        return _L.ishmemi_c_reduce_scatter_on_stream_deps(team, OPS[op], DTYPES[dtype], dest, source, nreduce,
+                                                          ret or None, stream or None, arr, len(hs),
+                                                          _event_handle(done))
+    return _L.ishmemi_c_reduce_scatter_on_stream(team, OPS[op], DTYPES[dtype], dest, source, nreduce,
+                                                 ret or None, stream or None)
+
+
+def _make_reduce_scatter(op: str, dt: str, on_stream: bool):
+    def fn(*args):
+        # ([team,] dest, source, nreduce) and ([team,] dest, source, nreduce, ret, stream).
+        k = 5 if on_stream else 3
+        if len(args) == k:
+            team = ISHMEM_TEAM_WORLD
+        elif len(args) == k + 1:
+            team, args = args[0], args[1:]
+        else:
+            raise TypeError("expected ([team,] dest, source, nreduce" + (", ret, stream)" if on_stream else ")"))
+        if on_stream:
+            return reduce_scatter_on_stream(op, dt, *args, team=team)
+        return reduce_scatter(op, dt, *args, team=team)
+    return fn
+
+
+# ishmemx_{tn}_{op}_reduce_scatter[_on_stream] for reduce's whole (op, typename) matrix and the two
+# 16-bit types; a list of its own (API_NAMES and HALF_NAMES are the reduce's).
+REDUCE_SCATTER_NAMES: list[str] = []
+for _op, _tns in TYPENAMES_FOR_OP.items():
+    for _tn in [*_tns, *(HALF_TYPENAMES if _op in ("max", "min", "sum", "prod") else [])]:
+        for _on in (False, True):
+            _name = f"ishmemx_{_tn}_{_op}_reduce_scatter{'_on_stream' if _on else ''}"
+            _f = _make_reduce_scatter(_op, TYPENAMES.get(_tn, _tn), _on)
+            _f.__name__ = _name
+            _f.__doc__ = f"{_name}([team,] dest, source, nreduce{', ret, stream' if _on else ''}) -> int"
+            setattr(_mod, _name, _f)
+            REDUCE_SCATTER_NAMES.append(_name)
+del _op, _tns, _tn, _on, _name, _f

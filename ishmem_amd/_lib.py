@@ -59,6 +59,9 @@ PROTOTYPES = [
     ("ishmemi_c_fcollect_on_stream", _i, [_i, _vp, _vp, _sz, _vp, _vp]),
     ("ishmemi_c_alltoall", _i, [_i, _vp, _vp, _sz]),
     ("ishmemi_c_alltoall_on_stream", _i, [_i, _vp, _vp, _sz, _vp, _vp]),
+    ("ishmemi_c_reduce_scatter", _i, [_i, _i, _i, _vp, _vp, _sz]),
+    ("ishmemi_c_reduce_scatter_on_stream", _i, [_i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
+    ("ishmemi_c_reduce_scatter_on_stream_deps", _i, [_i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
     ("ishmemi_c_collect_on_stream", _i, [_i, _vp, _vp, _sz, _vp, _vp]),
     ("ishmemi_c_put", _i, [_vp, _vp, _sz, _i]),
     ("ishmemi_c_get", _i, [_vp, _vp, _sz, _i]),

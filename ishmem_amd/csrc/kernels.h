@@ -135,11 +135,15 @@ struct LLArgs {
     //               token item (no source read) so every member still hears from every member;
     //   kLLAlltoall - the item pushed to member j is read from block j of the source
     //               (src + j * nbytes), member j's item lands at dest + j * nbytes; this member's
-    //               own block goes straight from src + me * nbytes to dest + me * nbytes.
+    //               own block goes straight from src + me * nbytes to dest + me * nbytes;
+    //   kLLReduceScatter - kLLAlltoall's send side (member j is pushed block j of the source, nbytes
+    //               per block) and kLLReduce's fold: dest (nbytes) = fold over the team of every
+    //               member's block `me` (ll_rs_kernel, a kernel of its own).
     int mode;
     int root;
 };
-constexpr int kLLReduce = 0, kLLInscan = 1, kLLExscan = 2, kLLCollect = 3, kLLBroadcast = 4, kLLAlltoall = 5;
+constexpr int kLLReduce = 0, kLLInscan = 1, kLLExscan = 2, kLLCollect = 3, kLLBroadcast = 4, kLLAlltoall = 5,
+              kLLReduceScatter = 6;
 hipError_t launch_ll(int op, int dt, const LLArgs &a, hipStream_t s);
 
 // fcollect / collect (all-gather of the members' sources): member j's bytes land at
@@ -258,6 +262,9 @@ struct PhaseArgs {
 };
 hipError_t launch_rs_phase(int op, int dt, const PhaseArgs &a, hipStream_t s);
 hipError_t launch_ag_phase(const PhaseArgs &a, hipStream_t s);
+// Element-granular one-shot fold (rs_elem_kernel; the reduce-scatter's blocks without a 16-B body):
+// dst[i] = fold over j of element i of src[j], a.nitems ELEMENTS; head / tail / shift unused.
+hipError_t launch_rs_elem(int op, int dt, const PhaseArgs &a, hipStream_t s);
 
 // Returns hipSuccess or a launch error.  `vec` selects the 16-B vector body (all operands
 // share the same address residue mod 16) or the element-granular path.

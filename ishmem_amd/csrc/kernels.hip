@@ -27,7 +27,8 @@ int phase_unaligned() { return g_phase_unaligned; }
                                       hipStream_t s);                                              \
     hipError_t launch_fanin_op##N(int dt, bool vec, const FaninArgs &a, int grid, hipStream_t s); \
     hipError_t launch_ll_op##N(int dt, const LLArgs &a, hipStream_t s);                            \
-    hipError_t launch_rs_phase_op##N(int dt, const PhaseArgs &a, hipStream_t s);
+    hipError_t launch_rs_phase_op##N(int dt, const PhaseArgs &a, hipStream_t s);                   \
+    hipError_t launch_rs_elem_op##N(int dt, const PhaseArgs &a, hipStream_t s);
 ISHMEMI_DECL_OP(0)
 ISHMEMI_DECL_OP(1)
 ISHMEMI_DECL_OP(2)
@@ -92,6 +93,21 @@ hipError_t launch_rs_phase(int op, int dt, const PhaseArgs &a, hipStream_t s)
         case 4: return launch_rs_phase_op4(dt, a, s);
         case 5: return launch_rs_phase_op5(dt, a, s);
         case 6: return launch_rs_phase_op6(dt, a, s);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_rs_elem(int op, int dt, const PhaseArgs &a, hipStream_t s)
+{
+    if (!op_dtype_valid(op, dt)) return hipErrorInvalidValue;
+    switch (op) {
+        case 0: return launch_rs_elem_op0(dt, a, s);
+        case 1: return launch_rs_elem_op1(dt, a, s);
+        case 2: return launch_rs_elem_op2(dt, a, s);
+        case 3: return launch_rs_elem_op3(dt, a, s);
+        case 4: return launch_rs_elem_op4(dt, a, s);
+        case 5: return launch_rs_elem_op5(dt, a, s);
+        case 6: return launch_rs_elem_op6(dt, a, s);
         default: return hipErrorInvalidValue;
     }
 }

@@ -28,6 +28,9 @@
 //     pushes its bytes as {4 B data, 32-bit epoch} granules into every peer's ring and folds what
 //     it receives; the same exchange carries small fcollect, sum scans and broadcasts (round 5),
 //     and small alltoalls, where each peer is pushed its own block of the source.
+//   * ll_rs_kernel / rs_elem_kernel: the reduce-scatter extension — the granule
+//     exchange with alltoall's send side and the reduce's fold, and the element-granular one-shot
+//     fold of blocks without a 16-B body; its 16-B body is rs_phase_kernel given new pointers.
 //   * The barriers replace ishmemi_team_sync's psync counters (src/collectives/sync_impl.h:30-69)
 //     with epoch-tagged flags in fine-grained memory: one "started" flag per member, one
 //     "ready" flag per reduced segment (the RS -> AG hand-off) and one "done reading" flag per
@@ -1398,6 +1401,110 @@ int phase_grid(K, uint64_t items)
     return (int) std::max<uint64_t>(1, std::min<uint64_t>(g, (uint64_t) kFaninMaxGrid));
 }
 
+// ---------------------------------------------------------------------------------------------
+// Element-granular fold of the reduce-scatter's barrier path (runtime.cpp reduce_scatter_heap): a
+// member's block `me` sits at me * B bytes into the source, so a block too short for the realigned
+// body (< kRealignMinBytes) on another 16-B phase than dest, or one whose address (or dest's) is no
+// multiple of the element size, has no 16-B body.  a.nitems ELEMENTS, a.src[j] = member j's block,
+// one element per thread, grid-stride, one-wave workgroups; never waits.  Every access is as wide as
+// its address allows (`unit`: the largest power of two <= sizeof(T) dividing the address; an
+// element's units are assembled in a register, so no access is ever misaligned): own block by plain
+// loads, peers' by system-scope (sc0 sc1) loads, the result by system-scope write-through stores.
+// ---------------------------------------------------------------------------------------------
+template <typename U, bool PEER>
+__device__ __forceinline__ uint64_t unit_load(const char *p)
+{
+    if constexpr (PEER) return (uint64_t) __hip_atomic_load((const U *) p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    else return (uint64_t) *(const U *) p;
+}
+
+template <typename T, bool PEER>
+__device__ __forceinline__ T elem_load(const char *p, uint32_t unit)
+{
+    using B = std::conditional_t<sizeof(T) == 8, uint64_t, std::conditional_t<sizeof(T) == 4, uint32_t,
+              std::conditional_t<sizeof(T) == 2, uint16_t, uint8_t>>>;
+    uint64_t v = 0;
+    if (unit >= sizeof(T)) {
+        v = unit_load<B, PEER>(p);
+    } else if (unit == 4) {
+        if constexpr (sizeof(T) > 4) v = unit_load<uint32_t, PEER>(p) | (unit_load<uint32_t, PEER>(p + 4) << 32);
+    } else if (unit == 2) {
+        if constexpr (sizeof(T) > 2) {
+#pragma unroll
+            for (uint32_t k = 0; k < sizeof(T) / 2; ++k) v |= unit_load<uint16_t, PEER>(p + 2 * k) << (16 * k);
+        }
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < sizeof(T); ++k) v |= unit_load<uint8_t, PEER>(p + k) << (8 * k);
+    }
+    return __builtin_bit_cast(T, (B) v);
+}
+
+template <typename U>
+__device__ __forceinline__ void unit_store(char *p, uint64_t v)
+{
+    __hip_atomic_store((U *) p, (U) v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+template <typename T>
+__device__ __forceinline__ void elem_store(char *p, uint32_t unit, T x)
+{
+    using B = std::conditional_t<sizeof(T) == 8, uint64_t, std::conditional_t<sizeof(T) == 4, uint32_t,
+              std::conditional_t<sizeof(T) == 2, uint16_t, uint8_t>>>;
+    const uint64_t v = (uint64_t) __builtin_bit_cast(B, x);
+    if (unit >= sizeof(T)) {
+        unit_store<B>(p, v);
+    } else if (unit == 4) {
+        if constexpr (sizeof(T) > 4) {
+            unit_store<uint32_t>(p, v);
+            unit_store<uint32_t>(p + 4, v >> 32);
+        }
+    } else if (unit == 2) {
+        if constexpr (sizeof(T) > 2) {
+#pragma unroll
+            for (uint32_t k = 0; k < sizeof(T) / 2; ++k) unit_store<uint16_t>(p + 2 * k, v >> (16 * k));
+        }
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < sizeof(T); ++k) unit_store<uint8_t>(p + k, v >> (8 * k));
+    }
+}
+
+// Largest power of two <= 8 that divides the address.
+__device__ __forceinline__ uint32_t addr_unit(const void *p)
+{
+    const uint32_t low = (uint32_t) (uintptr_t) p | 8u;
+    return low & (0u - low);
+}
+
+template <typename T, int OP>
+__global__ __launch_bounds__(kFaninBlock) void rs_elem_kernel(PhaseArgs a)
+{
+    const int p = a.p, me = a.me;
+    // Every member's block has this member's block address modulo 16 (heaps are mapped at the same
+    // offsets modulo a page), so one unit serves all p loads.
+    const uint32_t su = addr_unit(a.src[me]), du = addr_unit(a.dst);
+    const uint64_t stride = (uint64_t) gridDim.x * kFaninBlock;
+    for (uint64_t i = (uint64_t) blockIdx.x * kFaninBlock + threadIdx.x; i < a.nitems; i += stride) {
+        const uint64_t off = i * sizeof(T);
+        T acc = T();
+        for (int j = 0; j < p; ++j) {
+            const T x = j == me ? elem_load<T, false>(a.src[j] + off, su) : elem_load<T, true>(a.src[j] + off, su);
+            acc = j == 0 ? x : op1<T, OP>(acc, x);
+        }
+        elem_store<T>(a.dst + off, du, acc);
+    }
+}
+
+template <typename T, int OP>
+hipError_t rs_elem_t(const PhaseArgs &a, hipStream_t s)
+{
+    int g = phase_grid(rs_elem_kernel<T, OP>, a.nitems);
+    if (realign_grid_cap() > 0) g = std::min(g, realign_grid_cap());
+    hipLaunchKernelGGL((rs_elem_kernel<T, OP>), dim3(g), dim3(kFaninBlock), 0, s, a);
+    return hipGetLastError();
+}
+
 template <typename T, int OP>
 hipError_t rs_phase_t(const PhaseArgs &a, hipStream_t s)
 {
@@ -1543,6 +1650,70 @@ __global__ __launch_bounds__(kBlock) void ll_kernel(LLArgs a)
     kernel_epoch_done(a, ep);
 }
 
+// kLLReduceScatter: the ring exchange of ll_kernel with kLLAlltoall's send side and kLLReduce's
+// fold.  a.nbytes = B, one block; the source holds p blocks.  Thread t pushes item t of block j into
+// its slot of member j's ring for every j != me, polls its own ring for every peer's item t (their
+// block `me`), folds them with its own block `me` in canonical team order and stores at dest + 8t.
+// Items count from each block's base, so a block base off the 8-B grid only narrows ll_load /
+// ll_store.  Every member pushes to and hears from every member, as in every other mode, so the
+// rings' parity argument is unchanged and the modes may follow each other in any order.  A kernel
+// of its own: ll_kernel's code is what it was.
+template <typename T, int OP>
+__global__ __launch_bounds__(kBlock) void ll_rs_kernel(LLArgs a)
+{
+    const uint64_t first = (uint64_t) blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t stride = (uint64_t) gridDim.x * kBlock;
+    const uint64_t nitems = (a.nbytes + 7) / 8;
+    const int p = a.p, me = a.me;
+    const uint32_t ep = kernel_epoch(a);
+    const uint64_t par = ep & 1u;
+    const uint64_t tag = (uint64_t) ep << 32;
+    const uint64_t sg = ll_sender_granules(p);
+    for (uint64_t item = first; item < nitems; item += stride) {
+        const uint64_t off = item * 8;
+        const uint64_t valid = a.nbytes - off < 8 ? a.nbytes - off : 8;
+        for (int j = 0; j < p; ++j) {
+            if (j == me) continue;
+            const uint64_t x = ll_load(a.src + (uint64_t) j * a.nbytes + off, valid);
+            uint64_t *slot = a.peer_ring[j] + (par * (uint64_t) p + me) * sg;
+            __hip_atomic_store(slot + ll_granule(item, 0), tag | (uint32_t) x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            __hip_atomic_store(slot + ll_granule(item, 1), tag | (uint32_t) (x >> 32), __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+    }
+    const uint64_t t0 = __builtin_amdgcn_s_memrealtime();
+    bool ok = true;
+    for (uint64_t item = first; item < nitems && ok; item += stride) {
+        const uint64_t off = item * 8;
+        const uint64_t valid = a.nbytes - off < 8 ? a.nbytes - off : 8;
+        const uint64_t mine = ll_load(a.src + (uint64_t) me * a.nbytes + off, valid);
+        uint64_t acc = 0;
+        for (int j = 0; j < p && ok; ++j) {
+            uint64_t x = mine;
+            if (j != me) {
+                const uint64_t *slot = a.my_ring + (par * (uint64_t) p + j) * sg;
+                uint64_t h0, h1;
+                for (;;) {
+                    h0 = __hip_atomic_load(slot + ll_granule(item, 0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    h1 = __hip_atomic_load(slot + ll_granule(item, 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                    if ((h0 >> 32) == ep && (h1 >> 32) == ep) break;
+                    if (__builtin_amdgcn_s_memrealtime() - t0 > a.timeout_ticks) {
+                        ok = false;
+                        __hip_atomic_fetch_or(a.err, 1u << 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+                        break;
+                    }
+                    __builtin_amdgcn_s_sleep(1);
+                }
+                x = (h0 & 0xffffffffull) | (h1 << 32);
+            }
+            acc = j == 0 ? x : fold8<T, OP>(acc, x);
+        }
+        if (ok) ll_store(a.dst + off, valid, acc);
+    }
+    if (!ok && a.ret) __hip_atomic_fetch_or(a.ret, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    kernel_epoch_done(a, ep);
+}
+
 inline int resident_blocks_of(const void *kernel);
 
 template <typename T, int OP>
@@ -1550,6 +1721,11 @@ hipError_t ll_t(const LLArgs &a, hipStream_t s)
 {
     const uint64_t nitems = (a.nbytes + 7) / 8;
     const uint64_t want = std::max<uint64_t>(1, (nitems + kBlock - 1) / kBlock);
+    if (a.mode == kLLReduceScatter) {
+        const int grid = (int) std::min<uint64_t>(want, (uint64_t) resident_blocks_of((const void *) ll_rs_kernel<T, OP>));
+        hipLaunchKernelGGL((ll_rs_kernel<T, OP>), dim3(grid), dim3(kBlock), 0, s, a);
+        return hipGetLastError();
+    }
     const int grid = (int) std::min<uint64_t>(want, (uint64_t) resident_blocks_of((const void *) ll_kernel<T, OP>));
     hipLaunchKernelGGL((ll_kernel<T, OP>), dim3(grid), dim3(kBlock), 0, s, a);
     return hipGetLastError();

@@ -1610,6 +1610,126 @@ int alltoall_impl(int team, void *dst, const void *src, size_t nbytes, int *ret,
     return finish_call(s, team, st, blocking);
 }
 
+// ---------------- reduce-scatter (ishmemx_<TN>_<op>_reduce_scatter) ----------------
+// An extension: the first half of what every large reduce does.  Each member's source holds p blocks
+// of `n` elements (alltoall's source layout, symmetric heap); member k's dest (n elements, any
+// device-writable memory, written by its owner only) = the team-order fold of every member's block
+// k — bit for bit elements [k·n, (k+1)·n) of what reduce over p·n elements leaves in dest.  Two
+// paths, chosen by B = n·sizeof(T), the team and parameters agreed at init (never by dest's address,
+// which is not symmetric here):
+//   granule - B within ll_eligible and the ring capacity: ll_rs_kernel (kLLReduceScatter), one launch;
+//   barrier - team barrier (every source final), ONE one-shot fold grid, team barrier (every member
+//             has read every source): no all-gather and no middle barrier.
+// Which fold grid a member runs is its own business (the grids never wait and pair with nobody):
+// member k reads at byte offset k·B, so unless B is a multiple of 16 the members' blocks sit on
+// different 16-B phases.
+//
+// Local argument errors (n > 0), as bits so the blocking call can exchange them.
+constexpr uint64_t kRsSrcHeap = 1, kRsDest = 2, kRsOverlap = 4, kRsOpType = 8;
+uint64_t reduce_scatter_arg_errors(const State &s, const Team &t, int op, int dt, const void *dst, const void *src,
+                                   size_t n)
+{
+    if (!op_dtype_valid(op, dt)) return kRsOpType;
+    const uint64_t total = (uint64_t) t.size * n * dtype_size(dt);
+    const char *d = (const char *) dst, *sp = (const char *) src;
+    uint64_t e = 0;
+    // Peers find their block at this source's offset in their own heap: all p blocks inside it.
+    if (!in_heap(s, sp) || total > (uint64_t) (s.heap + s.heap_size - sp)) e |= kRsSrcHeap;
+    if (!dst || !device_writable(s, dst)) e |= kRsDest;
+    if (d < sp + total && sp < d + n * dtype_size(dt)) e |= kRsOverlap;
+    return e;
+}
+
+std::string reduce_scatter_arg_message(uint64_t e)
+{
+    if (e & kRsOpType) return "reduce_scatter: a member's (op, dtype) pair is invalid";
+    if (e & kRsSrcHeap) return "reduce_scatter: a member's source is not symmetric-heap memory (p blocks inside the heap; there is no staged path)";
+    if (e & kRsDest) return "reduce_scatter: a member's dest is not device-writable (heap, device or pinned host memory)";
+    return "reduce_scatter: a member's dest overlaps its source";
+}
+
+// The barrier path.  `dv`: dest as this device addresses it.
+int reduce_scatter_heap(State &s, int team, int op, int dt, char *dv, const void *src, size_t n, int *ret,
+                        hipStream_t st)
+{
+    if (order_stream(s, st)) return 1;
+    Team &t = s.teams[team];
+    const size_t es = dtype_size(dt);
+    const uint64_t B = (uint64_t) n * es;
+    ReduceArgs a;
+    std::string why;
+    if (barrier_args(s, team, ret, a, why)) return fail("reduce_scatter: " + why);
+    PhaseArgs ph;
+    memset(&ph, 0, sizeof(ph));
+    for (int j = 0; j < t.size; ++j) {
+        const int gpe = t.start + j * t.stride;
+        const char *pj = translate(s, src, gpe);
+        if (!pj) return fail("reduce_scatter: source not mapped for PE " + std::to_string(gpe));
+        ph.src[j] = pj + (uint64_t) t.my_idx * B;  // member j's block `me`
+    }
+    ph.dst = dv;
+    ph.elem = (uint32_t) es;
+    ph.p = t.size;
+    ph.me = t.my_idx;
+    ph.peer_nt = s.phased_peer_nt;
+    ph.whole = 1;
+    // This member's block and dest: d0 is this member's alone, s0 differs from member to member
+    // unless B is a multiple of 16.
+    const uintptr_t d0 = (uintptr_t) dv, s0 = (uintptr_t) src + (uintptr_t) ((uint64_t) t.my_idx * B);
+    const bool same_phase = ((d0 ^ s0) & 15) == 0;
+    const bool body = d0 % es == 0 && s0 % es == 0 && (same_phase || B >= kRealignMinBytes);
+    if (body) {
+        // rs_phase_kernel, whole = 1: items laid out by dest's phase; a block on another phase is read
+        // with unaligned 16-B loads (phase_unaligned 0: rs_phase_realign_kernel, whose aligned loads
+        // are bounded by `total` = B from the block's base, so the last member's never pass the end
+        // of the source).
+        const uint64_t h = std::min<uint64_t>(n, ((16 - d0 % 16) % 16) / es);
+        ph.head = h;
+        ph.nitems = (n - h) * es / 16;
+        ph.tail = n - h - ph.nitems * (16 / es);
+        ph.items_per_chunk = std::max<uint64_t>(ph.nitems, 1);
+        if (!same_phase) {
+            ph.shift = (uint32_t) ((s0 + h * es) % 16);
+            ph.total = B;
+        }
+        ph.xcd_group = s.rs_xcd && device_share() == 1 ? 1 : 0;  // reduce_heap's rule
+    } else {
+        ph.nitems = n;  // elements (rs_elem_kernel)
+    }
+    if (team_barrier(a, st)) return 1;
+    if (body) HIP_TRY(launch_rs_phase(op, dt, ph, st));
+    else HIP_TRY(launch_rs_elem(op, dt, ph, st));
+    return team_barrier(a, st);
+}
+
+// checked: the blocking call has already exchanged the members' argument errors.
+int reduce_scatter_impl(int team, int op, int dt, void *dst, const void *src, size_t n, int *ret, hipStream_t st,
+                        bool blocking, bool checked)
+{
+    State &s = S();
+    std::lock_guard<std::mutex> lk(s.mu);
+    if (team_call(s, "reduce_scatter", team)) return 1;
+    Team &t = s.teams[team];
+    if (!op_dtype_valid(op, dt)) return fail("reduce_scatter: invalid (op, dtype) pair");
+    if (n > 0 && (!dst || !src)) return fail("reduce_scatter: null buffer");
+    if (n > 0 && !checked) {
+        const uint64_t e = reduce_scatter_arg_errors(s, t, op, dt, dst, src, n);
+        if (e) return fail(reduce_scatter_arg_message(e));
+    }
+    const size_t B = n * dtype_size(dt);
+    if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));
+    if (t.size == 1) {
+        if (B && launch_copy(device_view(s, dst), src, B, st)) return 1;  // block 0, bits kept
+    } else if (n == 0) {
+        if (team_sync_locked(s, team, st, ret)) return 1;
+    } else if (ll_eligible(s, t, dst, src, B) && B <= ll_capacity(t.size)) {
+        if (reduce_ll(s, team, op, dt, device_view(s, dst), src, B, ret, st, kLLReduceScatter)) return 1;
+    } else if (reduce_scatter_heap(s, team, op, dt, device_view(s, dst), src, n, ret, st)) {
+        return 1;
+    }
+    return finish_call(s, team, st, blocking);
+}
+
 // ---------------- put / get (ishmem_put / ishmem_get, src/rma.cpp, src/rma_impl.h) ----------------
 // The first calls that STORE payload into a peer's heap (DESIGN.md §3b has the visibility contract).
 // One side is the peer's heap as mapped here (dest of a put, source of a get: given as this PE's
@@ -4122,6 +4242,44 @@ int ishmemi_c_alltoall_on_stream(int team, void *dest, const void *source, size_
     // Nothing can be exchanged on the host here: each member checks its own arguments and fails
     // before any launch (as collect_on_stream does).
     return alltoall_impl(team, dest, source, nbytes, ret, (hipStream_t) stream, false, false);
+}
+
+int ishmemi_c_reduce_scatter(int team, int op, int dtype, void *dest, const void *source, size_t nreduce)
+{
+    // As the blocking alltoall: the members agree on argument failures before anything is launched.
+    State &s = S();
+    bool checked = false;
+    if (member_call(s, team) && s.teams[team].size > 1 && nreduce > 0) {
+        const uint64_t e = reduce_scatter_arg_errors(s, s.teams[team], op, dtype, dest, source, nreduce);
+        uint64_t any = 0;
+        if (team_exchange(team, e ? (e | kAgreeFail) : 0, nullptr, &any)) return 1;
+        if (any & kAgreeFail) return fail(reduce_scatter_arg_message(e ? e : any));
+        checked = true;
+    }
+    return reduce_scatter_impl(team, op, dtype, dest, source, nreduce, nullptr, 0, true, checked);
+}
+
+int ishmemi_c_reduce_scatter_on_stream(int team, int op, int dtype, void *dest, const void *source, size_t nreduce,
+                                       int *ret, void *stream)
+{
+    // Nothing can be exchanged on the host here: each member checks its own arguments and fails
+    // before any launch.
+    return reduce_scatter_impl(team, op, dtype, dest, source, nreduce, ret, (hipStream_t) stream, false, false);
+}
+
+int ishmemi_c_reduce_scatter_on_stream_deps(int team, int op, int dtype, void *dest, const void *source,
+                                            size_t nreduce, int *ret, void *stream, void *const *deps, size_t ndeps,
+                                            void *done)
+{
+    hipStream_t st = (hipStream_t) stream;
+    if (ndeps && !deps) return fail("reduce_scatter_on_stream: deps is NULL with ndeps > 0");
+    for (size_t i = 0; i < ndeps; ++i) {
+        if (!deps[i]) return fail("reduce_scatter_on_stream: null dependency event");
+        HIP_TRY(hipStreamWaitEvent(st, (hipEvent_t) deps[i], 0));
+    }
+    if (reduce_scatter_impl(team, op, dtype, dest, source, nreduce, ret, st, false, false)) return 1;
+    if (done) HIP_TRY(hipEventRecord((hipEvent_t) done, st));
+    return 0;
 }
 
 int ishmemi_c_collect(int team, void *dest, const void *source, size_t nbytes)
