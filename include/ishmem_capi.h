@@ -520,8 +520,22 @@ int ishmemi_c_register_device_ctx_slot(const void *host_shadow);
  * round 5's fixed 16-slot block, for comparison; "flag_block_pool_bytes" = the exported team blocks
  * this PE holds in its pool, in use or free for the next split), "init_us_<phase>" (init's phases: hip, heap,
  * flags, bootstrap, ipc_heap, ipc_flags, teams, total; printed under ISHMEM_DEBUG=2), "cu_count"
- * (compute units of this PE's device) and "device_share" (PEs of the job on this PE's device: 1
- * with one PE per GPU). */
+ * (compute units of this PE's device), "device_share" (PEs of the job on this PE's device: 1
+ * with one PE per GPU) and "last_path" (read-only: the ishmemi_c_path_t below that this PE's most
+ * recent host or on-stream collective chose; a record for tests, it affects no choice). */
+typedef enum {
+    ISHMEMI_C_PATH_NONE = 0,       /* no collective yet, or a zero-size call (a team sync only) */
+    ISHMEMI_C_PATH_SINGLE = 1,     /* one-member team: a copy (an exclusive scan: a zero fill) */
+    ISHMEMI_C_PATH_GRANULE = 2,    /* the one-hop granule exchange (ll_kernel / ll_rs_kernel) */
+    ISHMEMI_C_PATH_FOLD = 3,       /* whole-array / direct fold between two barriers, the in-place scratch
+                                      fold and scan_direct_kernel included */
+    ISHMEMI_C_PATH_PHASED = 4,     /* one-shot grids between team barriers */
+    ISHMEMI_C_PATH_PERSISTENT = 5, /* the handshake kernels: allreduce_kernel (its two-member one-shot
+                                      mode included), scan_kernel, collect_kernel, collect_dyn_kernel */
+    ISHMEMI_C_PATH_ELEM = 6,       /* reduce-scatter's element-granular rs_elem_kernel */
+    ISHMEMI_C_PATH_STAGED = 7,     /* through the staging region (host or non-heap buffers) */
+    ISHMEMI_C_PATH_COUNT = 8
+} ishmemi_c_path_t;
 const char *ishmemi_c_last_error(void);
 int ishmemi_c_set_param(const char *name, long long value);
 long long ishmemi_c_get_param(const char *name);

@@ -236,6 +236,23 @@ def get_param(name: str) -> int:
     return int(_L.ishmemi_c_get_param(name.encode()))
 
 
+# ishmemi_c_path_t (include/ishmem_capi.h), by value.
+PATH_NAMES = ("none", "single", "granule", "fold", "phased", "persistent", "elem", "staged")
+
+
+def last_path() -> str:
+    """The path this PE's most recent host or on-stream collective chose (get_param "last_path")."""
+    return PATH_NAMES[get_param("last_path")]
+
+
+def path_limits(npes: int, colocated: bool) -> tuple[int, int]:
+    """(granule limit, fold bound) of a team of `npes` members (ishmemi_c_path_limits; no GPU needed)."""
+    ll, fold = ctypes.c_longlong(0), ctypes.c_longlong(0)
+    if _L.ishmemi_c_path_limits(npes, int(bool(colocated)), ctypes.byref(ll), ctypes.byref(fold)):
+        raise ValueError(f"path_limits: {last_error()}")
+    return ll.value, fold.value
+
+
 # ---- the reduction path ------------------------------------------------------------------
 def reduce(op: str, dtype: str, dest: int, source: int, nreduce: int, team: int = ISHMEM_TEAM_WORLD) -> int:
     """ishmemi_reduce<T,OP>(team, dest, source, nreduce) (src/collectives/reduce_impl.h:259-317)."""

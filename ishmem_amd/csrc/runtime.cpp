@@ -448,6 +448,9 @@ struct State {
     int ar_shifted = 1;
     // The shifted reduce-scatter's block order (PhaseArgs::xcd_group; set_param "rs_xcd", default 1).
     int rs_xcd = 1;
+    // The path this PE's most recent host or on-stream collective chose (ishmemi_c_path_t; get_param
+    // "last_path").  A record only: set where a call branches, read by nothing that chooses a path.
+    int last_path = ISHMEMI_C_PATH_NONE;
     // Two-member disjoint reduces up to oneshot_p2 bytes: barrier + one whole-array fold grid +
     // barrier (1, default) or the persistent kernel's one-shot mode (0; set_param "direct_p2",
     // alike on every PE).
@@ -1135,6 +1138,7 @@ int reduce_heap(State &s, int team, int op, int dt, void *dst, const void *src, 
         ph.me = t.my_idx;
         ph.peer_nt = s.phased_peer_nt;
         ph.whole = direct ? 1 : 0;
+        s.last_path = direct ? ISHMEMI_C_PATH_FOLD : ISHMEMI_C_PATH_PHASED;
         // XCD-grouped block order for shifted sources: only when this PE has its GPU to itself.  The
         // order assumes workgroup b runs on XCD b mod 8, which holds for a kernel running alone (1 GiB
         // a + b from sources 4 / 12 B off: 0.75 -> 0.83 of HBM, one process); with co-located PEs'
@@ -1183,6 +1187,7 @@ int reduce_heap(State &s, int team, int op, int dt, void *dst, const void *src, 
         pl.grid = (int) std::max<uint64_t>(
             1, std::min<uint64_t>(nsegs(pl.nitems, a.seg_items), (uint64_t) s.max_blocks));
     }
+    s.last_path = ISHMEMI_C_PATH_PERSISTENT;
     HIP_TRY(launch_allreduce(op, dt, pl.vec, a, pl.grid, st));
     return 0;
 }
@@ -1255,6 +1260,7 @@ int reduce_staged(State &s, int team, int op, int dt, void *dst, const void *src
         pins.pin(s, dst, bytes, di);
     }
     int rc = reduce_staged_pipeline(s, team, op, dt, dst, src, n, ret, st, di, si);
+    s.last_path = ISHMEMI_C_PATH_STAGED;  // whatever the chunks' in-place reduces took
     if (pins.any()) {
         // Every copy of the call has completed (also after a failure part-way) before unlocking.
         bool ok = hipStreamSynchronize(st) == hipSuccess;
@@ -1366,9 +1372,11 @@ int collect_launch(State &s, int team, void *dst, const void *src, const uint64_
     a.dst = (char *) dst;
     a.ret = ret;
     a.unit = (orv & 15) == 0 ? 16 : (orv & 3) == 0 ? 4 : 1;
+    s.last_path = ISHMEMI_C_PATH_PERSISTENT;
     if (t.size > 1 && (long long) off >= s.phased_min) {
         // Large: barrier, one-shot pull grid, barrier (kernels_coll.hip collect_phase_kernel).
         // Decided on the total bytes only, which every member knows, so all take the same path.
+        s.last_path = ISHMEMI_C_PATH_PHASED;
         ReduceArgs r;
         if (barrier_args(s, team, ret, r, why)) return fail("collect: " + why);
         if (team_barrier(r, st)) return 1;
@@ -1412,6 +1420,7 @@ int collect_staged(State &s, int team, char *dst, const char *src, const uint64_
         if (mine) HIP_TRY(hipMemcpyAsync(s.staging, src + k * S, mine, hipMemcpyDefault, st));
         if (collect_launch(s, team, dst, s.staging, segb, ret, st, segoff)) return 1;
     }
+    s.last_path = ISHMEMI_C_PATH_STAGED;
     return staging_release(s, st);
 }
 
@@ -1425,6 +1434,7 @@ int collect_on_stream_impl(int team, void *dst, const void *src, size_t nbytes, 
     Team &t = s.teams[team];
     if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));
     if (t.size == 1) {
+        s.last_path = ISHMEMI_C_PATH_SINGLE;
         if (nbytes && dst != src && launch_copy(dst, src, nbytes, st)) return 1;
         return mark_stream(s, st);
     }
@@ -1453,6 +1463,7 @@ int collect_on_stream_impl(int team, void *dst, const void *src, size_t nbytes, 
     const uint64_t tile = (uint64_t) kBlock * kUnroll * 16;
     const uint64_t g = ((uint64_t) t.size * nbytes + tile - 1) / tile;
     const int grid = (int) std::max<uint64_t>(8, std::min<uint64_t>(g, (uint64_t) s.max_blocks));
+    s.last_path = ISHMEMI_C_PATH_PERSISTENT;
     HIP_TRY(launch_collect_dyn(a, grid, st));
     return mark_stream(s, st);
 }
@@ -1469,6 +1480,7 @@ int fcollect_impl(int team, void *dst, const void *src, size_t nbytes, int *ret,
     Team &t = s.teams[team];
     if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));  // sticky: launches OR failures in
     if (t.size == 1) {
+        s.last_path = ISHMEMI_C_PATH_SINGLE;
         if (nbytes && dst != src && launch_copy(dst, src, nbytes, st)) return 1;
     } else {
         // staged >= 0: the blocking call has asked about dest already and exchanged the answer.
@@ -1479,8 +1491,10 @@ int fcollect_impl(int team, void *dst, const void *src, size_t nbytes, int *ret,
         // must agree on it).  Zero bytes: only the team synchronises.
         if (staged < 0) staged = in_heap(s, src) ? 0 : 1;
         if (nbytes == 0) {
+            s.last_path = ISHMEMI_C_PATH_NONE;
             if (team_sync_locked(s, team, st, ret)) return 1;
         } else if (!staged && ll_eligible(s, t, dst, src, nbytes) && 2 * nbytes <= ll_capacity(t.size)) {
+            s.last_path = ISHMEMI_C_PATH_GRANULE;
             // Small payloads (round 5): the granule exchange, every member's bytes stored at their
             // team-order offset (kLLCollect) — no start / done handshakes.  Up to half the ring's
             // capacity: the pull kernel moves (p-1)·B where the granules move 2(p-1)·B, and at
@@ -1590,10 +1604,13 @@ int alltoall_impl(int team, void *dst, const void *src, size_t nbytes, int *ret,
     }
     if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));
     if (t.size == 1) {
+        s.last_path = ISHMEMI_C_PATH_SINGLE;
         if (nbytes && dst != src && launch_copy(dst, src, nbytes, st)) return 1;
     } else if (nbytes == 0) {
+        s.last_path = ISHMEMI_C_PATH_NONE;
         if (team_sync_locked(s, team, st, ret)) return 1;
     } else if (ll_eligible(s, t, dst, src, nbytes) && 2 * nbytes <= ll_capacity(t.size)) {
+        s.last_path = ISHMEMI_C_PATH_GRANULE;
         if (reduce_ll(s, team, ISHMEMI_OP_OR, ISHMEMI_DT_UINT8, dst, src, nbytes, ret, st, kLLAlltoall)) return 1;
     } else {
         uint64_t nb[kMaxPes], off[kMaxPes];
@@ -1696,6 +1713,7 @@ int reduce_scatter_heap(State &s, int team, int op, int dt, char *dv, const void
     } else {
         ph.nitems = n;  // elements (rs_elem_kernel)
     }
+    s.last_path = body ? ISHMEMI_C_PATH_FOLD : ISHMEMI_C_PATH_ELEM;
     if (team_barrier(a, st)) return 1;
     if (body) HIP_TRY(launch_rs_phase(op, dt, ph, st));
     else HIP_TRY(launch_rs_elem(op, dt, ph, st));
@@ -1719,10 +1737,13 @@ int reduce_scatter_impl(int team, int op, int dt, void *dst, const void *src, si
     const size_t B = n * dtype_size(dt);
     if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));
     if (t.size == 1) {
+        s.last_path = ISHMEMI_C_PATH_SINGLE;
         if (B && launch_copy(device_view(s, dst), src, B, st)) return 1;  // block 0, bits kept
     } else if (n == 0) {
+        s.last_path = ISHMEMI_C_PATH_NONE;
         if (team_sync_locked(s, team, st, ret)) return 1;
     } else if (ll_eligible(s, t, dst, src, B) && B <= ll_capacity(t.size)) {
+        s.last_path = ISHMEMI_C_PATH_GRANULE;
         if (reduce_ll(s, team, op, dt, device_view(s, dst), src, B, ret, st, kLLReduceScatter)) return 1;
     } else if (reduce_scatter_heap(s, team, op, dt, device_view(s, dst), src, n, ret, st)) {
         return 1;
@@ -2445,7 +2466,9 @@ int scan_scratch(State &s, int team, int dt, int inclusive, void *dst, const voi
         a.items_per_chunk = items_per_chunk(m, t.size);
         a.inclusive = inclusive;
         const bool vec = (((uintptr_t) dst | (uintptr_t) src | (uintptr_t) s.staging) & 15) == 0;
-        if ((long long) (m * es) >= s.phased_min) {
+        const bool phased = (long long) (m * es) >= s.phased_min;
+        if (off == 0) s.last_path = phased ? ISHMEMI_C_PATH_PHASED : ISHMEMI_C_PATH_PERSISTENT;  // the first segment's
+        if (phased) {
             // Large segment: barrier, one-shot fold grid, barrier, one-shot pull grid, barrier
             // (kernels_coll.hip scan_p1_kernel / scan_p2_kernel).  Every member knows m.
             ReduceArgs r;
@@ -2477,9 +2500,11 @@ int scan_impl(int team, int dt, int inclusive, void *dst, const void *src, size_
     const size_t es = dtype_size(dt);
     if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));  // sticky over the segments
     if (t.size == 1) {  // inclusive: the source; exclusive: the sum of nothing
+        s.last_path = ISHMEMI_C_PATH_SINGLE;
         if (n && inclusive && dst != src && launch_copy(dst, src, n * es, st)) return 1;
         if (n && !inclusive) HIP_TRY(hipMemsetAsync(dst, 0, n * es, st));
     } else if (n == 0) {
+        s.last_path = ISHMEMI_C_PATH_NONE;
         if (team_sync_locked(s, team, st, ret)) return 1;
     } else {
         if (!in_heap(s, dst) || !in_heap(s, src)) return fail("scan: buffers must be symmetric-heap memory");
@@ -2492,6 +2517,7 @@ int scan_impl(int team, int dt, int inclusive, void *dst, const void *src, size_
         if (ll_eligible(s, t, dst, src, nb)) {
             // Small payloads (round 5): the granule exchange, each member folding members 0..me
             // (inclusive) or 0..me-1 (exclusive) — no scratch rows, no handshakes.
+            s.last_path = ISHMEMI_C_PATH_GRANULE;
             if (reduce_ll(s, team, ISHMEMI_OP_SUM, dt, dst, src, nb, ret, st, inclusive ? kLLInscan : kLLExscan))
                 return 1;
         } else if (ipc_max == 0) {
@@ -2505,6 +2531,7 @@ int scan_impl(int team, int dt, int inclusive, void *dst, const void *src, size_
             // four members under the reduce's whole-array bound (path_limits; 0 with direct_p2
             // off, so an A/B of direct_p2 switches reduces and scans together — ADVICE r05).
             if (order_stream(s, st)) return 1;
+            s.last_path = ISHMEMI_C_PATH_FOLD;
             ScanArgs a;
             memset(&a, 0, sizeof(a));
             std::string why;
@@ -2557,6 +2584,7 @@ int reduce_impl(int team, int op, int dt, void *dst, const void *src, size_t n, 
 
     if (t.size == 1) {
         // One PE: the reduction is a copy (reduce_impl.h:288-289 with no peers to fold).
+        s.last_path = ISHMEMI_C_PATH_SINGLE;
         if (n > 0 && dst != src) {
             const Kind kd = ptr_info(s, dst, di).kind(), ks = ptr_info(s, src, si).kind();
             if (kd == Kind::Host || ks == Kind::Host) {
@@ -2569,12 +2597,14 @@ int reduce_impl(int team, int op, int dt, void *dst, const void *src, size_t n, 
         }
     } else if (n == 0) {
         // The reference still synchronises the team (reduce_impl.h:244, :254).
+        s.last_path = ISHMEMI_C_PATH_NONE;
         if (team_sync_locked(s, team, st, ret)) return 1;
     } else if (ll_eligible(s, t, dst, src, bytes) && ptr_info(s, dst, di).kind() != Kind::Host &&
                ptr_info(s, src, si).kind() != Kind::Host) {
+        s.last_path = ISHMEMI_C_PATH_GRANULE;
         if (reduce_ll(s, team, op, dt, dst, src, bytes, ret, st)) return 1;
     } else if (in_heap(s, dst) && in_heap(s, src)) {
-        if (reduce_heap(s, team, op, dt, dst, src, n, ret, st)) return 1;
+        if (reduce_heap(s, team, op, dt, dst, src, n, ret, st)) return 1;  // fold, phased or persistent
     } else {
         if (reduce_staged(s, team, op, dt, dst, src, n, ret, st, di, si)) return 1;
     }
@@ -4364,6 +4394,7 @@ int ishmemi_c_broadcast_on_stream(int team, void *dest, const void *source, size
     hipStream_t st = (hipStream_t) stream;
     if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));
     if (t.size == 1) {
+        s.last_path = ISHMEMI_C_PATH_SINGLE;
         if (nbytes && dest != source) {
             if (device_writable(s, dest) && classify(s, source) != Kind::Host) {
                 if (launch_copy(dest, source, nbytes, st)) return 1;
@@ -4373,7 +4404,10 @@ int ishmemi_c_broadcast_on_stream(int team, void *dest, const void *source, size
         }
         return mark_stream(s, st);
     }
-    if (nbytes == 0) return team_sync_locked(s, team, st, ret) || mark_stream(s, st);
+    if (nbytes == 0) {
+        s.last_path = ISHMEMI_C_PATH_NONE;
+        return team_sync_locked(s, team, st, ret) || mark_stream(s, st);
+    }
     if (!in_heap(s, source)) return fail("broadcast_on_stream: source must be symmetric-heap memory");
     if (!device_writable(s, dest)) return fail("broadcast_on_stream: dest must be heap, device or pinned host memory");
     if (ll_eligible(s, t, dest, source, nbytes) && 2 * nbytes <= ll_capacity(t.size)) {
@@ -4381,6 +4415,7 @@ int ishmemi_c_broadcast_on_stream(int team, void *dest, const void *source, size
         // others one token each (kLLBroadcast) — no handshakes.  Dest is stored locally whatever
         // its kind, so every member decides alike from the byte count (round 6: the choice no
         // longer depends on this PE's dest being in the heap — ADVICE r05).
+        s.last_path = ISHMEMI_C_PATH_GRANULE;
         if (reduce_ll(s, team, ISHMEMI_OP_OR, ISHMEMI_DT_UINT8, dest, source, nbytes, ret, st, kLLBroadcast, root)) return 1;
         return mark_stream(s, st);
     }
@@ -4405,6 +4440,7 @@ int ishmemi_c_broadcast(int team, void *dest, const void *source, size_t nbytes,
     const int p = s.teams[team].size;
     if (root < 0 || root >= p) return fail("broadcast: root is not a team index");
     if (p == 1) {  // the root alone: dest = source, from or to any kind of memory
+        s.last_path = ISHMEMI_C_PATH_SINGLE;
         if (nbytes && dest != source) HIP_TRY(hipMemcpy(dest, source, nbytes, hipMemcpyDefault));
         return 0;
     }
@@ -4416,7 +4452,10 @@ int ishmemi_c_broadcast(int team, void *dest, const void *source, size_t nbytes,
     uint64_t all[kMaxPes], any = 0;
     if (team_exchange(team, mine, all, &any)) return 1;
     if (any & kAgreeFail) return fail("broadcast: a member's dest is not device-writable (heap, device or pinned host memory)");
-    if (nbytes == 0) return ishmemi_c_team_sync(team);
+    if (nbytes == 0) {
+        s.last_path = ISHMEMI_C_PATH_NONE;
+        return ishmemi_c_team_sync(team);
+    }
     uint64_t counts[kMaxPes] = {}, zero[kMaxPes] = {};
     counts[root] = nbytes;
     std::lock_guard<std::mutex> lk(s.mu);
@@ -4424,6 +4463,7 @@ int ishmemi_c_broadcast(int team, void *dest, const void *source, size_t nbytes,
         // Small payloads, the root's source in the heap (agreed above): the granule broadcast
         // (kLLBroadcast); the root reads its own source, the others none, and every member
         // stores its own dest, of any device-writable kind.
+        s.last_path = ISHMEMI_C_PATH_GRANULE;
         if (reduce_ll(s, team, ISHMEMI_OP_OR, ISHMEMI_DT_UINT8, dest, source, nbytes, nullptr, 0, kLLBroadcast, root))
             return 1;
     } else if (all[root] & kAgreeStaged) {
@@ -4544,6 +4584,7 @@ long long ishmemi_c_get_param(const char *name)
     if (n == "collect_realign") return collect_realign();
     if (n == "ar_shifted") return s.ar_shifted;
     if (n == "rs_xcd") return s.rs_xcd;
+    if (n == "last_path") return s.last_path;  // ishmemi_c_path_t of this PE's most recent collective
     if (n == "direct_p2") return s.direct_p2;
     if (n == "direct_inplace") return s.direct_inplace;
     if (n == "block_spin") return s.block_spin;

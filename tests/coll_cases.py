@@ -14,7 +14,8 @@ MIB = 1 << 20
 PHASED_DEFAULT = 4 * MIB  # ISHMEM_PHASED_MIN_BYTES when unset
 
 # Every size in the tables is far below the default thresholds, so the environment alone decides
-# the path.  -1 turns the phased path off.
+# the path.  -1 turns the phased path off.  (Payloads standing ON the thresholds, per topology:
+# tests/topology_cases.py.)
 ENVS = {
     "granule": {},
     "handshake": {"ISHMEM_LL_MAX_BYTES": 0, "ISHMEM_PHASED_MIN_BYTES": -1},

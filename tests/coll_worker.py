@@ -48,11 +48,11 @@ def coll_input(seed: int, member: int, nbytes: int) -> np.ndarray:
 def run(pe: int, npes: int, key: str, scenarios: list[str], q, env: dict | None = None, envname: str = "granule") -> None:
     fails: list[str] = []
     try:
-        for k, v in (env or {}).items():  # None removes the variable
+        for k, v in (env or {}).items():  # a list gives each PE its own value, None removes it
             if v is None:
                 os.environ.pop(k, None)
             else:
-                os.environ[k] = str(v)
+                os.environ[k] = str(v[pe] if isinstance(v, list) else v)
         import ishmem_amd as ish
         import oracle
         from ishmem_amd import hip
@@ -79,9 +79,11 @@ def run(pe: int, npes: int, key: str, scenarios: list[str], q, env: dict | None 
             fail(f"ll_capacity_bytes {ish.get_param('ll_capacity_bytes')} != {cc.ll_capacity(npes)}")
 
         def limits(p):
-            """The live (granule, fold) thresholds of a co-located team of p members."""
+            """The live (granule, fold) thresholds of a team of p members on this world's topology:
+            every team of a world on one GPU is co-located, every team of two or more of a world
+            with one PE per GPU is not (the library's own answer for TEAM_WORLD says which)."""
             ll, fold = ctypes.c_longlong(-7), ctypes.c_longlong(-7)
-            if L.ishmemi_c_path_limits(p, 1, ctypes.byref(ll), ctypes.byref(fold)):
+            if L.ishmemi_c_path_limits(p, int(ish.get_param("team_colocated")), ctypes.byref(ll), ctypes.byref(fold)):
                 raise RuntimeError(ish.last_error())
             if p == npes and (ll.value, fold.value) != (ish.get_param("ll_limit_bytes"), ish.get_param("fold_limit_bytes")):
                 fail(f"path_limits({p}) {ll.value, fold.value} != get_param's")

@@ -91,11 +91,11 @@ def byte_offset(name: str, es: int) -> int:
 def run(pe: int, npes: int, key: str, scenarios: list[str], q, env: dict | None = None) -> None:
     fails: list[str] = []
     try:
-        for k, v in (env or {}).items():  # None removes the variable
+        for k, v in (env or {}).items():  # a list gives each PE its own value, None removes it
             if v is None:
                 os.environ.pop(k, None)
             else:
-                os.environ[k] = str(v)
+                os.environ[k] = str(v[pe] if isinstance(v, list) else v)
         import ishmem_amd as ish
         from ishmem_amd import hip
 

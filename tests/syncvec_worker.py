@@ -27,7 +27,7 @@ def run(pe: int, npes: int, key: str, scenarios: list[str], q, env: dict | None 
             if v is None:
                 os.environ.pop(k, None)
             else:
-                os.environ[k] = str(v)
+                os.environ[k] = str(v[pe] if isinstance(v, list) else v)
         import ishmem_amd as ish
         from ishmem_amd import hip
 

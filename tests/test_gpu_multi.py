@@ -267,8 +267,10 @@ def test_one_pe_per_gpu_configuration_emulated(npes):
     env = {**TESTHOOKS, "ISHMEM_TEST_PCI_BUS": [f"fake-bus-{i}" for i in range(npes)], "ISHMEM_MAX_BLOCKS": 1024,
            "ISHMEM_PHASED_MIN_BYTES": "", "PHASED_WANT": 4 << 20, "COLOCATED_WANT": 0,
            "LL_LIMIT_WANT": expected(npes, False)[0]}
-    run_pes(npes, ["phasedparam", "pathparam", "golden", "inplace", "edge", "large", "graph", "tripwire"], env=env,
-            timeout=400)
+    # offsets / offsets_large: sources on other 16-B phases than dest while the device share is 1, so
+    # the shifted reduce-scatter runs in its XCD-grouped block order (the node's default).
+    run_pes(npes, ["phasedparam", "pathparam", "golden", "inplace", "offsets", "offsets_large", "edge", "large", "graph",
+                   "tripwire"], env=env, timeout=400)
 
 
 @pytest.mark.parametrize("npes", [2, 4])
@@ -313,7 +315,8 @@ def test_opposite_order_collectives_of_two_teams_one_pe_per_gpu_emulated(npes, s
     # one PE per GPU (4 hardware queues per process) is covered by the default 16.
     env = {**TESTHOOKS, "ISHMEM_TEST_PCI_BUS": [f"fake-bus-{i}" for i in range(npes)], "ISHMEM_MAX_BLOCKS": 1024,
            "ISHMEM_PHASED_MIN_BYTES": "", "ISHMEM_WAIT_SLOTS": slots}
-    run_pes(npes, ["opposite"], env=env, timeout=300)
+    # 2 PEs: the offset sweeps too (shifted sources with the device share at 1).
+    run_pes(npes, ["opposite"] + (["offsets", "offsets_large"] if npes == 2 else []), env=env, timeout=300)
 
 
 @pytest.mark.parametrize("path", ["phased", "persistent"])
