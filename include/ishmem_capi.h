@@ -559,6 +559,24 @@ int ishmemi_c_chunk_bounds(uint64_t nitems, int npes, int c, uint64_t *begin, ui
  * path_limits, or ISHMEM_XGMI_LL_MAX_BYTES / ISHMEM_XGMI_FOLD_MAX_BYTES).  Computed with the
  * current parameters (the defaults before init). */
 int ishmemi_c_path_limits(int npes, int colocated, long long *ll_limit, long long *fold_limit);
+/* Block order of a local fan-in (the one-member copy of a collective, ishmemi_c_combine): the
+ * runtime's rule as a pure function (no GPU, no runtime state; no reference counterpart).  *rec is
+ * the previous launch the rule learned from (zeroed: none); ranges holds nranges {begin, end}
+ * address pairs, dest first, at most ISHMEMI_C_FANIN_RANGES.  mode 1 / 2: returns 0 (ascending) /
+ * 1 (descending).  mode 0: returns 0 and leaves *rec untouched when `capturing` is set, when
+ * payload_bytes < min_bytes or when dest overlaps a source; otherwise returns the opposite of
+ * rec->order when rec->stream == stream and a range of *rec overlaps a new one, else 0, and stores
+ * the new launch and its order in *rec.  The runtime calls it with set_param "fanin_order" (mode,
+ * default 0) and "fanin_order_min_bytes" (ISHMEM_FANIN_ORDER_MIN_BYTES); get_param
+ * "last_fanin_order" reads the order of the most recent such launch (a record only). */
+#define ISHMEMI_C_FANIN_RANGES 17 /* dest + 16 sources */
+typedef struct {
+    int32_t valid, order, nranges, reserved;
+    uint64_t stream;
+    uint64_t ranges[2 * ISHMEMI_C_FANIN_RANGES];
+} ishmemi_c_fanin_record_t;
+int ishmemi_c_fanin_order(ishmemi_c_fanin_record_t *rec, int mode, long long min_bytes, int capturing,
+                          const void *stream, const uint64_t *ranges, int nranges, uint64_t payload_bytes);
 /* Native bootstrap self-test (no GPU needed): allgather of one int per PE + barrier.
  * Fills out[npes]; used by the multi-process CPU tests. */
 int ishmemi_c_bootstrap_selftest(int pe, int npes, const char *key, int value, int *out);

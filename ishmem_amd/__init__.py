@@ -253,6 +253,27 @@ def path_limits(npes: int, colocated: bool) -> tuple[int, int]:
     return ll.value, fold.value
 
 
+class FaninOrder:
+    """The runtime's block-order rule for local fan-ins as a pure function (ishmemi_c_fanin_order;
+    no GPU needed): an instance holds the record of the last launch the rule learned from."""
+
+    RANGES = 17  # ISHMEMI_C_FANIN_RANGES
+
+    def __init__(self):
+        self.rec = (ctypes.c_uint64 * (3 + 2 * self.RANGES))()  # ishmemi_c_fanin_record_t, zeroed
+
+    def __call__(self, dest: int, sources, nbytes: int, stream: int = 0, mode: int = 0, min_bytes: int = 0,
+                 capturing: bool = False) -> int:
+        """0 (ascending) or 1 (descending) for dest / sources of `nbytes` each on `stream`."""
+        ops = [dest, *sources]
+        r = (ctypes.c_uint64 * (2 * len(ops)))(*[x for p in ops for x in (p, p + nbytes)])
+        o = _L.ishmemi_c_fanin_order(ctypes.addressof(self.rec), mode, min_bytes, int(capturing), stream or None,
+                                     r, len(ops), nbytes)
+        if o < 0:
+            raise ValueError("fanin_order: invalid arguments")
+        return o
+
+
 # ---- the reduction path ------------------------------------------------------------------
 def reduce(op: str, dtype: str, dest: int, source: int, nreduce: int, team: int = ISHMEM_TEAM_WORLD) -> int:
     """ishmemi_reduce<T,OP>(team, dest, source, nreduce) (src/collectives/reduce_impl.h:259-317)."""

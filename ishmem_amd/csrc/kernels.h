@@ -231,6 +231,9 @@ struct FaninArgs {
     int realign;
     uint32_t shift[kMaxFanin];
     uint64_t total;
+    // 1: the body's workgroup-sized blocks run from the last down to the first (lanes inside a
+    // block still ascend); head and tail as ever.  Chosen per launch by runtime.cpp fanin_order.
+    int reverse;
 };
 
 // Phased reduce-scatter / all-gather of large payloads (p > 1, 16-B vector body): two one-shot

@@ -976,8 +976,14 @@ __global__ __launch_bounds__(kFaninBlock) void fanin_kernel(FaninArgs a)
     using Item = std::conditional_t<VEC, Vec<T>, T>;
     constexpr uint64_t IB = sizeof(Item);
     const uint64_t head_bytes = VEC ? a.head * sizeof(T) : 0;
-    const uint64_t stride = (uint64_t) gridDim.x * kFaninBlock;
-    for (uint64_t i = (uint64_t) blockIdx.x * kFaninBlock + threadIdx.x; i < a.nitems; i += stride) {
+    // Workgroup-sized blocks of the body, walked up from block 0 or, with a.reverse, down from the
+    // last one (runtime.cpp fanin_order: the high end is what the previous launch over the same
+    // buffers left in the Infinity Cache).  Lanes inside a block ascend either way, so a workgroup
+    // still moves one contiguous block, and every base below derives from the mapped block.
+    const uint64_t nblocks = (a.nitems + kFaninBlock - 1) / kFaninBlock;
+    for (uint64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
+        const uint64_t i = (a.reverse ? nblocks - 1 - b : b) * kFaninBlock + threadIdx.x;
+        if (i >= a.nitems) continue;
         const uint64_t off = head_bytes + i * IB;
         Item acc;
         if constexpr (NS == 1) {
@@ -1133,15 +1139,17 @@ __global__ __launch_bounds__(kRealignBlock) void fanin_realign_kernel(FaninArgs 
     static_assert(NS == 1 || NS == 2, "realigned fan-in: 1 or 2 sources");
     __shared__ u32x4 edge[NS][kRealignWaves + 1];
     const uint32_t tid = threadIdx.x;
-    const uint64_t stride = (uint64_t) gridDim.x * kRealignBlock;
-    const uint64_t first = (uint64_t) blockIdx.x * kRealignBlock;
-    if (stride >= a.nitems) {
+    // Blocks of kRealignBlock items in ascending or (a.reverse) descending order, as in
+    // fanin_kernel; a block's bases, its edge load included, derive from the mapped block.
+    const uint64_t nblocks = (a.nitems + kRealignBlock - 1) / kRealignBlock;
+    auto first_item = [&](uint64_t b) { return (a.reverse ? nblocks - 1 - b : b) * kRealignBlock; };
+    if (gridDim.x >= nblocks) {
         // One block per workgroup (up to 2^31 items = 32 GiB): the grid-stride loop's bookkeeping
         // cost 1.3 % on the copy (var8, tools/realign_variants.hip).
-        if (first < a.nitems) fanin_realign_block<T, OP, NS>(a, edge, first);
+        if (blockIdx.x < nblocks) fanin_realign_block<T, OP, NS>(a, edge, first_item(blockIdx.x));
     } else {
-        for (uint64_t i0 = first; i0 < a.nitems; i0 += stride) {
-            fanin_realign_block<T, OP, NS>(a, edge, i0);
+        for (uint64_t b = blockIdx.x; b < nblocks; b += gridDim.x) {
+            fanin_realign_block<T, OP, NS>(a, edge, first_item(b));
             __syncthreads();  // edge[] is rewritten by the next pass
         }
     }

@@ -251,7 +251,7 @@ void warn_unknown_env()
         "MPI_LIB_NAME", "PMI_LIB_NAME", "TEAMS_MAX", "TEAM_SHARED_ONLY_SELF", "RUNTIME", "RUNTIME_USE_OSHMPI", "ROOT",
         // this library's
         "PE", "NPES", "DEVICE", "BOOTSTRAP_KEY", "TIMEOUT_MS", "MAX_BLOCKS", "WAIT_SLOTS", "LL_MAX_BYTES",
-        "ONESHOT_P2_MAX_BYTES", "PHASED_MIN_BYTES", "PHASED_PEER_NT", "STAGING_SIZE", "STAGING_SLOTS",
+        "ONESHOT_P2_MAX_BYTES", "PHASED_MIN_BYTES", "FANIN_ORDER_MIN_BYTES", "PHASED_PEER_NT", "STAGING_SIZE", "STAGING_SLOTS",
         "STAGED_COPY_KERNEL", "STREAM_ORDER", "FLAGS_KIND", "EP_UNCACHED", "BARRIER_KIND", "XGMI_LL_MAX_BYTES",
         "XGMI_FOLD_MAX_BYTES", "PUT_SIGNAL_FUSED_MAX_BYTES", "TEST_FLAGS_UNAVAILABLE", "TEST_PCI_BUS",
         // the Python package, build and bench harness
@@ -306,6 +306,11 @@ struct PoolBlock {
     bool in_use = false;
 };
 
+// The automatic block order of the local fan-in (fanin_order below) applies from this payload per
+// operand up: the smallest size of the 16 MiB - 4 GiB sweep from which it won at every larger one,
+// for the copy and for a + b alike (profiles/fanin_order/sweep.jsonl; at 16 - 32 MiB
+// alternating orders ran 5 - 18 % slower than one order, at 64 - 256 MiB the same within 0.2 %).
+constexpr long long kFaninOrderMinDefault = 512ll << 20;
 constexpr long long kPhasedOff = std::numeric_limits<long long>::max();
 // Round 3 put the threshold at 16 MiB: 2 PEs x 1 GiB 0.84 ms phased against 0.99-1.13 ms
 // persistent; 2 PEs x 32 / 64 MiB 36 / 59 us against the two-member one-shot fold's 42 / 78 us;
@@ -451,6 +456,14 @@ struct State {
     // The path this PE's most recent host or on-stream collective chose (ishmemi_c_path_t; get_param
     // "last_path").  A record only: set where a call branches, read by nothing that chooses a path.
     int last_path = ISHMEMI_C_PATH_NONE;
+    // Block order of the local fan-in over the caller's operands (fanin_order below): the mode
+    // (set_param "fanin_order": 0 automatic, 1 forward, 2 reverse), the automatic rule's lower bound
+    // (ISHMEM_FANIN_ORDER_MIN_BYTES, set_param "fanin_order_min_bytes"), the last such launch it
+    // learned from, and the order of the most recent one (get_param "last_fanin_order", a record only).
+    int fanin_order_mode = 0;
+    long long fanin_order_min = kFaninOrderMinDefault;
+    ishmemi_c_fanin_record_t fanin_rec = {};
+    int last_fanin_order = 0;
     // Two-member disjoint reduces up to oneshot_p2 bytes: barrier + one whole-array fold grid +
     // barrier (1, default) or the persistent kernel's one-shot mode (0; set_param "direct_p2",
     // alike on every PE).
@@ -792,7 +805,74 @@ void plan_fanin(FaninArgs &f, Plan &pl, const void *dst, const void *const *srcs
                                                              (uint64_t) kRealignMaxGrid));
 }
 
-int launch_copy(void *dst, const void *src, size_t bytes, hipStream_t st)
+// ---------------- block order of the local fan-in ----------------------------
+// A fan-in over operands larger than the Infinity Cache ends with the high end of every operand
+// resident and the low end evicted; the next ascending launch over the same memory evicts that
+// before it reaches it.  Walking the blocks down instead starts on what is still on-die.  The
+// choice is a pure function of the previous local fan-in (the record) and the new one, so it is
+// tested without a GPU (ishmemi_c_fanin_order):
+//   mode 1 / 2       - forward / reverse, whatever the operands;
+//   mode 0 (auto)    - forward, record untouched, when the stream is capturing (a graph would bake
+//                      one order in), the payload is below min_bytes, or dest overlaps a source;
+//                      else the opposite of the recorded order when the recorded launch ran on the
+//                      same stream and any operand range of it overlaps one of the new launch
+//                      (the same buffers again, or the last dest as the new source), else forward;
+//                      the new launch becomes the record.
+// Ranges are {begin, end} address pairs, dest first.
+using FaninRecord = ishmemi_c_fanin_record_t;
+
+bool ranges_overlap(uint64_t a0, uint64_t a1, uint64_t b0, uint64_t b1) { return a0 < b1 && b0 < a1; }
+
+int fanin_order(FaninRecord &rec, int mode, long long min_bytes, bool capture, const void *stream,
+                const uint64_t *ranges, int nranges, uint64_t payload_bytes)
+{
+    nranges = std::max(1, std::min(nranges, ISHMEMI_C_FANIN_RANGES));
+    bool self_overlap = false;
+    for (int j = 1; j < nranges; ++j)
+        self_overlap = self_overlap || ranges_overlap(ranges[0], ranges[1], ranges[2 * j], ranges[2 * j + 1]);
+    const bool exempt = capture || (long long) std::min<uint64_t>(payload_bytes, INT64_MAX) < min_bytes || self_overlap;
+    if (mode == 0 && exempt) return 0;
+    int order = mode == 2 ? 1 : 0;
+    if (mode == 0 && rec.valid && rec.stream == (uint64_t) (uintptr_t) stream) {
+        bool hit = false;
+        for (int i = 0; i < rec.nranges && !hit; ++i)
+            for (int j = 0; j < nranges && !hit; ++j)
+                hit = ranges_overlap(rec.ranges[2 * i], rec.ranges[2 * i + 1], ranges[2 * j], ranges[2 * j + 1]);
+        if (hit) order = !rec.order;
+    }
+    if (exempt) return order;  // a forced order on an exempt launch: nothing to learn from it
+    rec.valid = 1;
+    rec.order = order;
+    rec.stream = (uint64_t) (uintptr_t) stream;
+    rec.nranges = nranges;
+    memcpy(rec.ranges, ranges, sizeof(uint64_t) * 2 * (size_t) nranges);
+    return order;
+}
+
+bool capturing(hipStream_t st);
+
+// The order of a fan-in over the caller's own operands (s.mu held): fanin_order on the runtime's
+// record and parameters.  The capture query is skipped where the answer cannot matter.
+int choose_fanin_order(State &s, const void *dst, const void *const *srcs, int nsrc, size_t bytes, hipStream_t st)
+{
+    uint64_t r[2 * ISHMEMI_C_FANIN_RANGES];
+    r[0] = (uint64_t) (uintptr_t) dst;
+    r[1] = r[0] + bytes;
+    for (int j = 0; j < nsrc; ++j) {
+        r[2 * j + 2] = (uint64_t) (uintptr_t) srcs[j];
+        r[2 * j + 3] = r[2 * j + 2] + bytes;
+    }
+    const bool cap = s.fanin_order_mode == 0 && (long long) bytes >= s.fanin_order_min && capturing(st);
+    s.last_fanin_order = fanin_order(s.fanin_rec, s.fanin_order_mode, s.fanin_order_min, cap, st, r, nsrc + 1, bytes);
+    return s.last_fanin_order;
+}
+
+// kForward: the library's own traffic (staging slots, the in-place scratch), always ascending.
+// kChoose: the caller's buffers on the caller's stream (the one-member paths of the collectives):
+// the order fanin_order picks; the caller holds s.mu.
+enum class CopyOrder { kForward, kChoose };
+
+int launch_copy(void *dst, const void *src, size_t bytes, hipStream_t st, CopyOrder whose)
 {
     if (bytes == 0 || dst == src) return 0;
     FaninArgs f{};
@@ -802,6 +882,7 @@ int launch_copy(void *dst, const void *src, size_t bytes, hipStream_t st)
     const void *srcs[1] = {src};
     Plan pl;
     plan_fanin(f, pl, dst, srcs, 1, bytes, 1);
+    f.reverse = whose == CopyOrder::kChoose ? choose_fanin_order(S(), dst, srcs, 1, bytes, st) : 0;
     HIP_TRY(launch_fanin(ISHMEMI_OP_OR, ISHMEMI_DT_UINT8, pl.vec, f, pl.grid, st));
     return 0;
 }
@@ -1176,7 +1257,7 @@ int reduce_heap(State &s, int team, int op, int dt, void *dst, const void *src, 
         if (mark(4)) return 1;
         if (team_barrier(a, st)) return 1;
         if (mark(5)) return 1;
-        if (inplace_fold && launch_copy(dst, scratch, nb, st)) return 1;
+        if (inplace_fold && launch_copy(dst, scratch, nb, st, CopyOrder::kForward)) return 1;
         s.phase_recorded = s.phase_recorded || ev;
         return 0;
     }
@@ -1302,7 +1383,7 @@ int reduce_staged_pipeline(State &s, int team, int op, int dt, void *dst, const 
         const size_t m = std::min(chunk, n - off);
         if (used[sl]) HIP_TRY(hipStreamWaitEvent(s.copy_in, s.ev_out[sl], 0));  // slot drained
         if (src_dev) {
-            if (launch_copy(buf, src_dev + off * es, m * es, s.copy_in)) return 1;
+            if (launch_copy(buf, src_dev + off * es, m * es, s.copy_in, CopyOrder::kForward)) return 1;
         } else {
             HIP_TRY(hipMemcpyAsync(buf, (const char *) src + off * es, m * es, hipMemcpyDefault, s.copy_in));
         }
@@ -1318,7 +1399,7 @@ int reduce_staged_pipeline(State &s, int team, int op, int dt, void *dst, const 
         HIP_TRY(hipEventRecord(s.ev_red[sl], st));
         HIP_TRY(hipStreamWaitEvent(s.copy_out, s.ev_red[sl], 0));
         if (dst_dev) {
-            if (launch_copy(dst_dev + off * es, buf, m * es, s.copy_out)) return 1;
+            if (launch_copy(dst_dev + off * es, buf, m * es, s.copy_out, CopyOrder::kForward)) return 1;
         } else {
             HIP_TRY(hipMemcpyAsync((char *) dst + off * es, buf, m * es, hipMemcpyDefault, s.copy_out));
         }
@@ -1435,7 +1516,7 @@ int collect_on_stream_impl(int team, void *dst, const void *src, size_t nbytes, 
     if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));
     if (t.size == 1) {
         s.last_path = ISHMEMI_C_PATH_SINGLE;
-        if (nbytes && dst != src && launch_copy(dst, src, nbytes, st)) return 1;
+        if (nbytes && dst != src && launch_copy(dst, src, nbytes, st, CopyOrder::kChoose)) return 1;
         return mark_stream(s, st);
     }
     if (!in_heap(s, dst)) return fail("collect: dest must be symmetric-heap memory");
@@ -1481,7 +1562,7 @@ int fcollect_impl(int team, void *dst, const void *src, size_t nbytes, int *ret,
     if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));  // sticky: launches OR failures in
     if (t.size == 1) {
         s.last_path = ISHMEMI_C_PATH_SINGLE;
-        if (nbytes && dst != src && launch_copy(dst, src, nbytes, st)) return 1;
+        if (nbytes && dst != src && launch_copy(dst, src, nbytes, st, CopyOrder::kChoose)) return 1;
     } else {
         // staged >= 0: the blocking call has asked about dest already and exchanged the answer.
         if (staged < 0 && !device_writable(s, dst)) return fail("fcollect: dest must be heap, device or pinned host memory");
@@ -1605,7 +1686,7 @@ int alltoall_impl(int team, void *dst, const void *src, size_t nbytes, int *ret,
     if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));
     if (t.size == 1) {
         s.last_path = ISHMEMI_C_PATH_SINGLE;
-        if (nbytes && dst != src && launch_copy(dst, src, nbytes, st)) return 1;
+        if (nbytes && dst != src && launch_copy(dst, src, nbytes, st, CopyOrder::kChoose)) return 1;
     } else if (nbytes == 0) {
         s.last_path = ISHMEMI_C_PATH_NONE;
         if (team_sync_locked(s, team, st, ret)) return 1;
@@ -1738,7 +1819,7 @@ int reduce_scatter_impl(int team, int op, int dt, void *dst, const void *src, si
     if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));
     if (t.size == 1) {
         s.last_path = ISHMEMI_C_PATH_SINGLE;
-        if (B && launch_copy(device_view(s, dst), src, B, st)) return 1;  // block 0, bits kept
+        if (B && launch_copy(device_view(s, dst), src, B, st, CopyOrder::kForward)) return 1;  // block 0, bits kept
     } else if (n == 0) {
         s.last_path = ISHMEMI_C_PATH_NONE;
         if (team_sync_locked(s, team, st, ret)) return 1;
@@ -2501,7 +2582,7 @@ int scan_impl(int team, int dt, int inclusive, void *dst, const void *src, size_
     if (ret) HIP_TRY(hipMemsetAsync(ret, 0, sizeof(int), st));  // sticky over the segments
     if (t.size == 1) {  // inclusive: the source; exclusive: the sum of nothing
         s.last_path = ISHMEMI_C_PATH_SINGLE;
-        if (n && inclusive && dst != src && launch_copy(dst, src, n * es, st)) return 1;
+        if (n && inclusive && dst != src && launch_copy(dst, src, n * es, st, CopyOrder::kChoose)) return 1;
         if (n && !inclusive) HIP_TRY(hipMemsetAsync(dst, 0, n * es, st));
     } else if (n == 0) {
         s.last_path = ISHMEMI_C_PATH_NONE;
@@ -2591,7 +2672,7 @@ int reduce_impl(int team, int op, int dt, void *dst, const void *src, size_t n, 
                 // Host buffers take the same HBM-staged pipeline as on a multi-PE team, so the
                 // path's host-to-host rate is the one reported in DESIGN.md.
                 if (reduce_staged(s, team, op, dt, dst, src, n, ret, st, di, si)) return 1;
-            } else if (launch_copy(dst, src, bytes, st)) {
+            } else if (launch_copy(dst, src, bytes, st, CopyOrder::kChoose)) {
                 return 1;
             }
         }
@@ -2789,6 +2870,8 @@ int init_impl(int pe, int npes, int device, const std::string &key)
     s.oneshot_p2 = std::max<long long>(0, env_bytes("ISHMEM_ONESHOT_P2_MAX_BYTES", 32ll << 20));
     s.phased_min = env_bytes("ISHMEM_PHASED_MIN_BYTES", kPhasedDefault);
     if (s.phased_min < 0) s.phased_min = kPhasedOff;
+    s.fanin_order_min = std::max<long long>(0, env_bytes("ISHMEM_FANIN_ORDER_MIN_BYTES", kFaninOrderMinDefault));
+    s.fanin_rec = {};
     s.staging_bytes = (env_size("ISHMEM_STAGING_SIZE", (size_t) 128 << 20) + kHeapAlign - 1) &
                       ~(size_t) (kHeapAlign - 1);
     s.staging_slots = (int) std::min<long long>(kMaxStagingSlots, std::max<long long>(2, env_ll("ISHMEM_STAGING_SLOTS", kStagingSlotsDefault)));
@@ -4190,6 +4273,9 @@ int ishmemi_c_combine(int op, int dtype, void *dst, const void *const *srcs, int
     f.nsrc = nsrc;
     Plan pl;
     plan_fanin(f, pl, dst, srcs, nsrc, n, dtype_size(dtype));
+    State &s = S();
+    std::lock_guard<std::mutex> lk(s.mu);
+    f.reverse = choose_fanin_order(s, dst, srcs, nsrc, n * dtype_size(dtype), (hipStream_t) stream);
     HIP_TRY(launch_fanin(op, dtype, pl.vec, f, pl.grid, (hipStream_t) stream));
     return 0;
 }
@@ -4397,7 +4483,7 @@ int ishmemi_c_broadcast_on_stream(int team, void *dest, const void *source, size
         s.last_path = ISHMEMI_C_PATH_SINGLE;
         if (nbytes && dest != source) {
             if (device_writable(s, dest) && classify(s, source) != Kind::Host) {
-                if (launch_copy(dest, source, nbytes, st)) return 1;
+                if (launch_copy(dest, source, nbytes, st, CopyOrder::kChoose)) return 1;
             } else {
                 HIP_TRY(hipMemcpyAsync(dest, source, nbytes, hipMemcpyDefault, st));
             }
@@ -4519,6 +4605,11 @@ int ishmemi_c_set_param(const char *name, long long value)
     else if (n == "stream_order") s.stream_order = value != 0;
     else if (n == "oneshot_p2_max_bytes") s.oneshot_p2 = std::max<long long>(0, value);
     else if (n == "phased_min_bytes") s.phased_min = value < 0 ? kPhasedOff : value;
+    else if (n == "fanin_order") {  // per PE: the local fan-in touches no peer
+        if (value < 0 || value > 2) return fail("set_param: fanin_order is 0 (automatic), 1 (forward) or 2 (reverse)");
+        s.fanin_order_mode = (int) value;
+    }
+    else if (n == "fanin_order_min_bytes") s.fanin_order_min = std::max<long long>(0, value);
     else if (n == "ll_max_bytes") s.ll_max_bytes = std::min<long long>((long long) kLLMaxBytes, std::max<long long>(0, value));
     else if (n == "put_signal_fused_max_bytes") s.put_signal_fused_max = std::max<long long>(0, value);  // per PE
     else if (n == "debug") s.debug = (int) value;
@@ -4585,6 +4676,9 @@ long long ishmemi_c_get_param(const char *name)
     if (n == "ar_shifted") return s.ar_shifted;
     if (n == "rs_xcd") return s.rs_xcd;
     if (n == "last_path") return s.last_path;  // ishmemi_c_path_t of this PE's most recent collective
+    if (n == "fanin_order") return s.fanin_order_mode;
+    if (n == "fanin_order_min_bytes") return s.fanin_order_min;
+    if (n == "last_fanin_order") return s.last_fanin_order;  // 0 ascending, 1 descending: the last chosen launch
     if (n == "direct_p2") return s.direct_p2;
     if (n == "direct_inplace") return s.direct_inplace;
     if (n == "block_spin") return s.block_spin;
@@ -4646,6 +4740,13 @@ int ishmemi_c_path_limits(int npes, int colocated, long long *ll_limit, long lon
     *ll_limit = r.ll;
     *fold_limit = r.fold;
     return 0;
+}
+
+int ishmemi_c_fanin_order(ishmemi_c_fanin_record_t *rec, int mode, long long min_bytes, int capture,
+                          const void *stream, const uint64_t *ranges, int nranges, uint64_t payload_bytes)
+{
+    if (!rec || !ranges || nranges < 1 || nranges > ISHMEMI_C_FANIN_RANGES || mode < 0 || mode > 2) return -1;
+    return fanin_order(*rec, mode, min_bytes, capture != 0, stream, ranges, nranges, payload_bytes);
 }
 
 int ishmemi_c_bootstrap_selftest(int pe, int npes, const char *key, int value, int *out)
