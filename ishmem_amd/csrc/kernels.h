@@ -59,6 +59,23 @@ constexpr int kEpAgHead = 3;   // next all-gather item to grab
 constexpr int kEpStarted = 4;  // workgroups that have started (the first announces the launch)
 constexpr int kEpFail = 5;     // nonzero once any wait of this launch timed out: drain at once
 constexpr int kEpP1Done = 6;   // scan: phase-1 pieces completed
+// The epoch `n` launches after epoch `e` under kernel_epoch's rule (kernels_impl.h): e + 1, and
+// 0xFFFFFFFF -> 2.  0 (the words' initial value) and 1 (a team's first launch) are left once and
+// never come back, so the epochs cycle through [2, 0xFFFFFFFF] with the even period kEpochPeriod
+// and consecutive epochs always differ in parity.
+constexpr uint64_t kEpochPeriod = 0xFFFFFFFEull;  // 2^32 - 2
+inline uint32_t epoch_after(uint32_t e, uint64_t n)
+{
+    for (; e < 2 && n > 0; --n) ++e;
+    if (n == 0) return e;
+    return (uint32_t) (2 + ((uint64_t) e - 2 + n) % kEpochPeriod);
+}
+// Launches of one team after which the host refreshes the team's flag rows, ring granules and claim
+// words (runtime.cpp team_refresh): the flag waits compare in half range ((int32_t) (v - ep) >= 0),
+// which orders two epochs only while they are less than 2^31 launches apart; the granule and claim
+// tests compare for equality, which repeats after kEpochPeriod.  2^30 plus the launches of one call
+// stays under both.
+constexpr uint64_t kRefreshLaunches = 1ull << 30;
 // Arguments of the multi-PE reduce-scatter + all-gather kernel.  All pointers are already
 // translated into this process's address space (own heap or IPC-mapped peer heap).
 struct ReduceArgs {
@@ -275,6 +292,19 @@ hipError_t launch_allreduce(int op, int dt, bool vec, const ReduceArgs &a, int g
                             hipStream_t s);
 hipError_t launch_fanin(int op, int dt, bool vec, const FaninArgs &a, int grid, hipStream_t s);
 hipError_t launch_team_sync(const ReduceArgs &a, hipStream_t s);
+// Refresh of one team's words on this PE (team_refresh_kernel; runtime.cpp team_refresh runs it
+// between two team barriers, ishmemi_c_resync with nothing in flight on any PE): every word of the
+// flag block becomes `epoch`, every ring granule and claim word 0.  from_words = 1: the epoch is
+// the team's kEpEpoch (the barrier just before) and row (kPhaseSync, 0) is left alone — a peer
+// that has finished its refresh may already be storing the next barrier's epoch there.
+struct RefreshArgs {
+    uint32_t *my_flags;  // own team flag block (kFlagWordsPerTeam words)
+    uint64_t *my_ring;   // own ring (kLLTeamBytes)
+    uint32_t *ep_ctr;    // team's launch words
+    uint32_t epoch;
+    int from_words;
+};
+hipError_t launch_team_refresh(const RefreshArgs &a, hipStream_t s);
 // xGMI measurement hook: dst = sum of a.nsrc f32 arrays (a.nitems 16-B items), source loads with
 // cache policy 0 = nt, 1 = sc0 sc1.
 hipError_t launch_pull_probe(const FaninArgs &a, int policy, hipStream_t s);

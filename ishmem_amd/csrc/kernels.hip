@@ -127,4 +127,10 @@ hipError_t launch_team_sync(const ReduceArgs &a, hipStream_t s)
     return hipGetLastError();
 }
 
+hipError_t launch_team_refresh(const RefreshArgs &a, hipStream_t s)
+{
+    hipLaunchKernelGGL(team_refresh_kernel, dim3(kRefreshGrid), dim3(kBlock), 0, s, a);
+    return hipGetLastError();
+}
+
 }  // namespace ishmemi

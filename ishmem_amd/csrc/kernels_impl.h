@@ -309,8 +309,12 @@ __device__ __forceinline__ void launch_fail(const A &a, int phase)
 }
 
 // All threads call.  Wave 0 polls row (phase, slot) of the local flag block until the slot of
-// every member selected by `who` holds `ep` or a later epoch (wrap-safe): who = -1 every other
-// member, -2 every member including this one, >= 0 that member only.  Bounded: false on timeout
+// every member selected by `who` holds `ep` or a later epoch: who = -1 every other
+// member, -2 every member including this one, >= 0 that member only.  "Or later" is the half-range
+// test (int32_t) (v - ep) >= 0: it survives the 32-bit wrap, but only while the row's value is less
+// than 2^31 launches older than `ep` — an older value (or the 0 of a row never written) reads as
+// later and satisfies the wait.  The host keeps every row that fresh: it refreshes the team's words
+// every kRefreshLaunches launches (runtime.cpp team_refresh).  Bounded: false on timeout
 // (recorded in the team's error word) or once another workgroup of this launch has timed out.
 // No acquire instruction follows: every load of bytes another PE produced is a system-coherent
 // (sc0 sc1) load, which neither L1 nor a stale L2 line can satisfy; the wavefront fence only
@@ -1747,6 +1751,27 @@ __global__ __launch_bounds__(kBlock) void team_sync_kernel(ReduceArgs a)
     if (threadIdx.x == 0 && !ok && a.ret)
         __hip_atomic_fetch_or(a.ret, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     kernel_epoch_done(a, ep);
+}
+
+// Refresh of this PE's words of one team (kernels.h RefreshArgs): a grid-stride sweep that waits for
+// nothing and takes no epoch of its own.  The flag block and the ring are memory peers write with
+// system-scope stores; the same stores here, so a later launch's polls find these values.
+constexpr int kRefreshGrid = 256;
+__global__ __launch_bounds__(kBlock) void team_refresh_kernel(RefreshArgs a)
+{
+    const uint32_t ep = a.from_words ? __hip_atomic_load(a.ep_ctr + kEpEpoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM)
+                                     : a.epoch;
+    const uint64_t first = (uint64_t) blockIdx.x * kBlock + threadIdx.x;
+    const uint64_t stride = (uint64_t) gridDim.x * kBlock;
+    const uint64_t sync_row = ((uint64_t) kPhaseSync * kMaxBlocks) * kMaxPes;
+    for (uint64_t i = first; i < kFlagWordsPerTeam; i += stride) {
+        if (a.from_words && i >= sync_row && i < sync_row + kMaxPes) continue;
+        __hip_atomic_store(a.my_flags + i, ep, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    for (uint64_t i = first; i < kLLTeamBytes / 8; i += stride)
+        __hip_atomic_store(a.my_ring + i, (uint64_t) 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    for (uint64_t i = first; i < (uint64_t) kMaxBlocks; i += stride)
+        __hip_atomic_store(a.ep_ctr + kEpClaimLine * kLineWords + i, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // Canonical kernel type: MIN/MAX keep the signedness, every other integer op folds on the

@@ -388,6 +388,13 @@ struct State {
     ishmemi_c_device_ctx_t *dctx = nullptr;  // device copy of the device-API context
     uint32_t *dev_epochs = nullptr;
     uint32_t *kern_ep = nullptr;  // [team][kEpTeamWords] launch words of the host-launched kernels
+    // Per team: epoch-taking launches this PE enqueued since the team's words were last refreshed
+    // (note_launch, team_refresh; get_param "team_launches").  Every member makes the same calls
+    // on a team in the same order, so the counts agree without communication.  An upper bound of the
+    // device epoch's advance, except under graph replay (epochs).
+    uint64_t team_launches[kMaxTeams] = {};
+    uint64_t refresh_every = kRefreshLaunches;  // 0: never (set_param "test_refresh_every", test build)
+    int test_epoch_team = 0;                    // set_param "test_epoch_team" (test build)
 
     char *team_scratch = nullptr;  // small symmetric buffer for team-management collectives
     char *count_slots = nullptr;   // symmetric, one 64-B line per team: collect_on_stream counts
@@ -690,6 +697,12 @@ int team_args(State &s, int team, ReduceArgs &a, std::string &why)
     a.ep_ctr = s.kern_ep + (size_t) kEpTeamWords * team;
     return 0;
 }
+
+// Before every launch of a kernel that takes an epoch of the team whose launch words are `ep_ctr`
+// (the persistent reduce / collect / scan, the granule kernels, the team barrier): one filled
+// argument struct serves several such launches (the phased paths' barriers), so the count is kept
+// here, at the launch, not where the struct is filled.
+void note_launch(State &s, const uint32_t *ep_ctr) { ++s.team_launches[(size_t) (ep_ctr - s.kern_ep) / kEpTeamWords]; }
 
 int check_team_errors(State &s, int team)
 {
@@ -1033,6 +1046,7 @@ int host_wait(State &s, hipStream_t st)
 // choice one PE could make differently from its peers — so round 6 removed it.
 int team_barrier(const ReduceArgs &a, hipStream_t st)
 {
+    note_launch(S(), a.ep_ctr);
     HIP_TRY(launch_team_sync(a, st));
     return 0;
 }
@@ -1052,6 +1066,42 @@ int order_stream(State &s, hipStream_t st)
     if (!s.stream_order) return 0;
     if (s.last_stream_set && s.last_stream != st && !capturing(st))
         HIP_TRY(hipStreamWaitEvent(st, s.order_ev, 0));
+    return 0;
+}
+
+// Refresh of the team's words on `st`: barrier, this PE's sweep (team_refresh_kernel: flag rows to
+// the first barrier's epoch, ring granules and claim words to 0), barrier.  The first barrier ends
+// every earlier launch of the team on every member, so nobody stores into this PE's rows or ring
+// during the sweep except a peer already in the second barrier (whose row the sweep leaves alone);
+// the second keeps a member's next launch from pushing into a ring still being swept.  Every value
+// left behind is older than every later epoch and younger than 2^31 launches: no later wait takes it
+// for its own (epochs).
+int team_refresh(State &s, int team, hipStream_t st)
+{
+    ReduceArgs b;
+    std::string why;
+    if (barrier_args(s, team, nullptr, b, why)) return fail("refresh: " + why);
+    RefreshArgs r{};
+    r.my_flags = b.my_flags;
+    r.my_ring = s.tmem[team].ring[s.pe];
+    r.ep_ctr = b.ep_ctr;
+    r.from_words = 1;
+    if (!r.my_flags || !r.my_ring) return fail("refresh: team " + std::to_string(team) + " has no flag block or ring on this PE");
+    s.team_launches[team] = 0;
+    if (team_barrier(b, st)) return 1;
+    HIP_TRY(launch_team_refresh(r, st));
+    return team_barrier(b, st);
+}
+
+// Before the launches of a collective of `team` on `st`: stream order, and the team's refresh once
+// its launch count has reached the bound.  Every member reaches this point with the same count, so
+// all of them refresh or none.  Never under capture (a graph would replay the refresh, not the
+// decision): the next uncaptured call makes up for it.
+int begin_launches(State &s, int team, hipStream_t st)
+{
+    if (order_stream(s, st)) return 1;
+    if (s.refresh_every && s.team_launches[team] >= s.refresh_every && s.teams[team].size > 1 && !capturing(st))
+        return team_refresh(s, team, st);
     return 0;
 }
 
@@ -1095,7 +1145,7 @@ int staging_release(State &s, hipStream_t st)
 int reduce_ll(State &s, int team, int op, int dt, void *dst, const void *src, size_t bytes, int *ret,
               hipStream_t st, int mode = kLLReduce, int root = 0)
 {
-    if (order_stream(s, st)) return 1;
+    if (begin_launches(s, team, st)) return 1;
     Team &t = s.teams[team];
     LLArgs a;
     memset(&a, 0, sizeof(a));
@@ -1116,6 +1166,7 @@ int reduce_ll(State &s, int team, int op, int dt, void *dst, const void *src, si
     a.me = t.my_idx;
     a.mode = mode;
     a.root = root;
+    note_launch(s, a.ep_ctr);
     HIP_TRY(launch_ll(op, dt, a, st));
     return 0;
 }
@@ -1124,7 +1175,7 @@ int reduce_ll(State &s, int team, int op, int dt, void *dst, const void *src, si
 int reduce_heap(State &s, int team, int op, int dt, void *dst, const void *src, size_t n, int *ret,
                 hipStream_t st)
 {
-    if (order_stream(s, st)) return 1;
+    if (begin_launches(s, team, st)) return 1;
     Team &t = s.teams[team];
     const size_t es = dtype_size(dt);
     ReduceArgs a;
@@ -1269,6 +1320,7 @@ int reduce_heap(State &s, int team, int op, int dt, void *dst, const void *src, 
             1, std::min<uint64_t>(nsegs(pl.nitems, a.seg_items), (uint64_t) s.max_blocks));
     }
     s.last_path = ISHMEMI_C_PATH_PERSISTENT;
+    note_launch(s, a.ep_ctr);
     HIP_TRY(launch_allreduce(op, dt, pl.vec, a, pl.grid, st));
     return 0;
 }
@@ -1363,7 +1415,7 @@ int reduce_staged_pipeline(State &s, int team, int op, int dt, void *dst, const 
     const size_t slot_bytes = (s.staging_bytes / (size_t) nslots) & ~(kHeapAlign - 1);
     const size_t chunk = (slot_bytes / es) & ~size_t(63);
     if (chunk == 0) return fail("reduce: staging region too small");
-    if (order_stream(s, st)) return 1;
+    if (begin_launches(s, team, st)) return 1;
     if (!s.copy_in) {
         HIP_TRY(hipStreamCreateWithFlags(&s.copy_in, hipStreamNonBlocking));
         HIP_TRY(hipStreamCreateWithFlags(&s.copy_out, hipStreamNonBlocking));
@@ -1434,7 +1486,7 @@ int collect_launch(State &s, int team, void *dst, const void *src, const uint64_
                    hipStream_t st, const uint64_t *dst_off = nullptr, const char *const *srcs = nullptr)
 {
     Team &t = s.teams[team];
-    if (order_stream(s, st)) return 1;
+    if (begin_launches(s, team, st)) return 1;
     CollectArgs a;
     memset(&a, 0, sizeof(a));
     std::string why;
@@ -1467,6 +1519,7 @@ int collect_launch(State &s, int team, void *dst, const void *src, const uint64_
     }
     const uint64_t items = maxb / a.unit, tile = (uint64_t) kBlock * kUnroll;
     const int grid = (int) std::max<uint64_t>(1, std::min<uint64_t>((items + tile - 1) / tile, s.max_blocks));
+    note_launch(s, a.ep_ctr);
     HIP_TRY(launch_collect(a, grid, st));
     return 0;
 }
@@ -1523,7 +1576,7 @@ int collect_on_stream_impl(int team, void *dst, const void *src, size_t nbytes, 
     // Peers' sources are found at the offset of this PE's (symmetric) source, so it must be in
     // the heap even when this PE contributes nothing.
     if (!in_heap(s, src)) return fail("collect: source must be symmetric-heap memory");
-    if (order_stream(s, st)) return 1;
+    if (begin_launches(s, team, st)) return 1;
     CollectArgs a;
     memset(&a, 0, sizeof(a));
     std::string why;
@@ -1545,6 +1598,7 @@ int collect_on_stream_impl(int team, void *dst, const void *src, size_t nbytes, 
     const uint64_t g = ((uint64_t) t.size * nbytes + tile - 1) / tile;
     const int grid = (int) std::max<uint64_t>(8, std::min<uint64_t>(g, (uint64_t) s.max_blocks));
     s.last_path = ISHMEMI_C_PATH_PERSISTENT;
+    note_launch(s, a.ep_ctr);
     HIP_TRY(launch_collect_dyn(a, grid, st));
     return mark_stream(s, st);
 }
@@ -1585,7 +1639,7 @@ int fcollect_impl(int team, void *dst, const void *src, size_t nbytes, int *ret,
             // also required a non-host dest, which one member could pass alone — ADVICE r05).
             if (reduce_ll(s, team, ISHMEMI_OP_OR, ISHMEMI_DT_UINT8, dst, src, nbytes, ret, st, kLLCollect)) return 1;
         } else if (staged) {
-            if (order_stream(s, st) || collect_staged(s, team, (char *) dst, (const char *) src, nb, ret, st)) return 1;
+            if (begin_launches(s, team, st) || collect_staged(s, team, (char *) dst, (const char *) src, nb, ret, st)) return 1;
         } else if (collect_launch(s, team, dst, src, nb, ret, st)) {
             return 1;
         }
@@ -1750,7 +1804,7 @@ std::string reduce_scatter_arg_message(uint64_t e)
 int reduce_scatter_heap(State &s, int team, int op, int dt, char *dv, const void *src, size_t n, int *ret,
                         hipStream_t st)
 {
-    if (order_stream(s, st)) return 1;
+    if (begin_launches(s, team, st)) return 1;
     Team &t = s.teams[team];
     const size_t es = dtype_size(dt);
     const uint64_t B = (uint64_t) n * es;
@@ -2529,7 +2583,7 @@ int scan_scratch(State &s, int team, int dt, int inclusive, void *dst, const voi
 {
     const Team &t = s.teams[team];
     const size_t es = dtype_size(dt);
-    if (order_stream(s, st) || staging_acquire(s, st)) return 1;
+    if (begin_launches(s, team, st) || staging_acquire(s, st)) return 1;
     for (uint64_t off = 0; off < n; off += seg) {
         const uint64_t m = std::min<uint64_t>(seg, n - off);
         ScanArgs a;
@@ -2564,6 +2618,7 @@ int scan_scratch(State &s, int team, int dt, int inclusive, void *dst, const voi
         const uint64_t tile = (uint64_t) kBlock * 2 * (vec ? 16 / es : 1);
         const int grid = (int) std::max<uint64_t>(
             1, std::min<uint64_t>((a.items_per_chunk + tile - 1) / tile, s.max_blocks));
+        note_launch(s, a.ep_ctr);
         HIP_TRY(launch_scan(dt, a, vec, grid, st));
     }
     return staging_release(s, st);
@@ -2611,7 +2666,7 @@ int scan_impl(int team, int dt, int inclusive, void *dst, const void *src, size_
             // against the scratch kernel's 17.8-18.1 / 19.7-20.8 (profiles/r05/scan/).  Three and
             // four members under the reduce's whole-array bound (path_limits; 0 with direct_p2
             // off, so an A/B of direct_p2 switches reduces and scans together — ADVICE r05).
-            if (order_stream(s, st)) return 1;
+            if (begin_launches(s, team, st)) return 1;
             s.last_path = ISHMEMI_C_PATH_FOLD;
             ScanArgs a;
             memset(&a, 0, sizeof(a));
@@ -2639,7 +2694,7 @@ int team_sync_locked(State &s, int team, hipStream_t st, int *ret)
 {
     Team &t = s.teams[team];
     if (t.size <= 1) return 0;
-    if (order_stream(s, st)) return 1;
+    if (begin_launches(s, team, st)) return 1;
     ReduceArgs a;
     std::string why;
     if (barrier_args(s, team, ret, a, why)) return fail("team_sync: " + why);
@@ -3185,6 +3240,7 @@ int init_impl(int pe, int npes, int device, const std::string &key)
         HIP_TRY(hipMalloc((void **) &s.kern_ep, ep_bytes));
     }
     HIP_TRY(hipMemset(s.kern_ep, 0, ep_bytes));
+    for (uint64_t &c : s.team_launches) c = 0;
     // ... and, behind the epochs, the line of the device calls' wait_until_any / test_any rotor.
     HIP_TRY(hipMalloc((void **) &s.dev_epochs, kMaxTeams * sizeof(uint32_t) + 64));
     HIP_TRY(hipMemset(s.dev_epochs, 0, kMaxTeams * sizeof(uint32_t) + 64));
@@ -3860,6 +3916,7 @@ int ishmemi_c_team_split_strided(int parent, int start, int stride, int size, in
             hipMemset(s.dev_epochs + slot, 0, sizeof(uint32_t)) != hipSuccess ||
             hipMemset(s.kern_ep + (size_t) kEpTeamWords * slot, 0, kEpTeamWords * sizeof(uint32_t)) != hipSuccess)
             return fail("team_split_strided: flag reset failed");
+        s.team_launches[slot] = 0;  // a new or reused slot: zeroed words, a block zeroed before export
         if (sync_device_ctx(s)) return 1;
         if (hipDeviceSynchronize() != hipSuccess) return fail("team_split_strided: sync failed");
     }
@@ -4167,8 +4224,11 @@ int ishmemi_c_resync(void)
     // out advanced, a PE that never arrived did not), so every later collective of the team would
     // time out too.  The reference aborts the job instead (src/proxy.cpp:79-84).  Here every PE,
     // with no collective of its own in flight, agrees on the wrap-safe maximum of every team's
-    // epochs (host and device-API launches) over the bootstrap; every flag row and ring granule
-    // then holds an epoch <= the new one, so the next launch starts clean on every member.
+    // epochs (host and device-API launches) over the bootstrap, and sets its own words of every
+    // team to it (team_refresh_kernel: flag rows to the agreed epoch, ring granules and claim words
+    // to 0 — after the exchange, when no PE has anything in flight that could store into them).
+    // Every flag row and ring granule then holds an epoch <= the new one and less than 2^31 behind
+    // it, so the next launch starts clean on every member.
     State &s = S();
     std::lock_guard<std::mutex> lk(s.mu);
     if (!s.initialized) return fail("resync: not initialized");
@@ -4199,7 +4259,18 @@ int ishmemi_c_resync(void)
         w[kEpEpoch] = h;
         for (int r = 0; r < kEpReplicas; ++r) w[(kEpRepLine + r) * kLineWords] = h;
         mine.dev[t] = d;
+        s.team_launches[t] = 0;
+        const TeamMem &m = s.tmem[t];
+        if (s.teams[t].valid && s.teams[t].my_idx >= 0 && s.teams[t].size > 1 && m.flags[s.pe] && m.ring[s.pe]) {
+            RefreshArgs r{};
+            r.my_flags = m.flags[s.pe];
+            r.my_ring = m.ring[s.pe];
+            r.ep_ctr = s.kern_ep + (size_t) kEpTeamWords * t;
+            r.epoch = h;
+            HIP_TRY(launch_team_refresh(r, 0));
+        }
     }
+    HIP_TRY(hipDeviceSynchronize());  // the sweeps' claim words, before the copy below rewrites the block
     HIP_TRY(hipMemcpy(s.kern_ep, words.data(), words.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(s.dev_epochs, mine.dev, sizeof(mine.dev), hipMemcpyHostToDevice));
     for (int t = 0; t <= kMaxTeams; ++t) __atomic_store_n(&s.err_host[t], 0u, __ATOMIC_RELEASE);
@@ -4416,7 +4487,7 @@ int ishmemi_c_collect(int team, void *dest, const void *source, size_t nbytes)
     for (int j = 0; j < p; ++j) counts[j] &= ~(kAgreeStaged | kAgreeFail);
     std::lock_guard<std::mutex> lk(s.mu);
     if (any & kAgreeStaged) {
-        if (order_stream(s, 0) || collect_staged(s, team, (char *) dest, (const char *) source, counts, nullptr, 0))
+        if (begin_launches(s, team, 0) || collect_staged(s, team, (char *) dest, (const char *) source, counts, nullptr, 0))
             return 1;
     } else if (collect_launch(s, team, dest, source, counts, nullptr, 0)) {
         return 1;
@@ -4553,7 +4624,7 @@ int ishmemi_c_broadcast(int team, void *dest, const void *source, size_t nbytes,
         if (reduce_ll(s, team, ISHMEMI_OP_OR, ISHMEMI_DT_UINT8, dest, source, nbytes, nullptr, 0, kLLBroadcast, root))
             return 1;
     } else if (all[root] & kAgreeStaged) {
-        if (order_stream(s, 0) || collect_staged(s, team, (char *) dest, (const char *) source, counts, nullptr, 0))
+        if (begin_launches(s, team, 0) || collect_staged(s, team, (char *) dest, (const char *) source, counts, nullptr, 0))
             return 1;
     } else {
         const char *srcs[kMaxPes];
@@ -4635,6 +4706,35 @@ int ishmemi_c_set_param(const char *name, long long value)
             for (hipEvent_t &e : s.phase_ev) HIP_TRY(hipEventCreate(&e));
         s.phase_events = value != 0;
     }
+#ifdef ISHMEMI_TEST_HOOKS
+    // Test build only (the product library answers "unknown parameter").  test_epoch_advance n, with
+    // 0 < n < 2^31: called by every member with nothing of the team in flight, makes the launch
+    // words of team test_epoch_team on this PE what n more launches would have left — kEpEpoch and
+    // its replicas at epoch_after(e, n), every other launch word zero — and adds n to the team's
+    // launch count.  No flag row, ring granule or claim word is touched: the history it stands for
+    // is n launches that did not reach them.  test_refresh_every k: refresh after k launches
+    // instead of kRefreshLaunches, 0 never.
+    else if (n == "test_epoch_team") {
+        if (!member_call(s, (int) value)) return fail("set_param: test_epoch_team: invalid team or caller not a member");
+        s.test_epoch_team = (int) value;
+    }
+    else if (n == "test_epoch_advance") {
+        const int team = s.test_epoch_team;
+        if (!member_call(s, team)) return fail("set_param: test_epoch_advance: invalid team or caller not a member");
+        if (value <= 0 || value >= (1ll << 31)) return fail("set_param: test_epoch_advance needs 0 < n < 2^31");
+        uint32_t *w = s.kern_ep + (size_t) kEpTeamWords * team;
+        std::vector<uint32_t> words((size_t) kEpClaimLine * kLineWords, 0u);  // up to the claim words
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(words.data(), w + kEpEpoch, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        const uint32_t e = epoch_after(words[0], (uint64_t) value);
+        words[kEpEpoch] = e;
+        for (int r = 0; r < kEpReplicas; ++r) words[(size_t) (kEpRepLine + r) * kLineWords] = e;
+        HIP_TRY(hipMemcpy(w, words.data(), words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipDeviceSynchronize());
+        s.team_launches[team] += (uint64_t) value;
+    }
+    else if (n == "test_refresh_every") s.refresh_every = (uint64_t) std::max<long long>(0, value);
+#endif
     else return fail("set_param: unknown parameter " + n);
     return 0;
 }
@@ -4691,6 +4791,22 @@ long long ishmemi_c_get_param(const char *name)
     if (n == "heap_bytes") return (long long) s.heap_size;
     if (n == "device_share") return device_share();  // PEs of the job on this PE's device
     if (n == "launch_words") return (long long) (uintptr_t) s.kern_ep;  // debug: device address
+    // Launches counted since the team's last refresh: "team_launches" (TEAM_WORLD) or "team_launches:<team>".
+    if (n.rfind("team_launches", 0) == 0) {
+        int team = 0;
+        if (n.size() > 13 && (n[13] != ':' || sscanf(n.c_str() + 14, "%d", &team) != 1)) return -1;
+        return team >= 0 && team < kMaxTeams ? (long long) s.team_launches[team] : -1;
+    }
+    if (n == "refresh_launches") return (long long) s.refresh_every;
+    // Pure (no GPU, no library state), for tests/epoch_cases.py: the words of one team's launch
+    // block, where its claim words start, and "epoch_after:<e>:<n>" = epoch_after(e, n).
+    if (n == "launch_team_words") return kEpTeamWords;
+    if (n == "launch_claim_word") return kEpClaimLine * kLineWords;
+    if (n.rfind("epoch_after:", 0) == 0) {
+        unsigned long long e = 0, k = 0;
+        if (sscanf(n.c_str() + 12, "%llu:%llu", &e, &k) != 2 || e > 0xFFFFFFFFull) return -1;
+        return (long long) epoch_after((uint32_t) e, k);
+    }
     if (n == "cu_count") {
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) != hipSuccess ||
